@@ -9,9 +9,12 @@ N>1: weak scaling, 4096 instances per GPU, instances sharded contiguously over r
 collective: they are independent), one RCCL all-gather of the solved dq + status shards per step
 (opensot_amd/parallel.py: the same ShardGather / ShardedCycle / timed_steps the gloo tests run).
 
-After the timed region rank 0 also measures, OUTSIDE the headline: the other BASELINE configurations at their per-GPU
-sizes and the kinematics producer (`other_configs`), the CPU reference path on the host cores (`cpu_baseline`, a thread
-sweep), and the parity of the headline batch against qpOASES with per-instance KKT / lexicographic evidence (`parity`).
+A plain run sets up, warms up, times the --steps steps, writes the last step's outputs where --dump-outputs asks for them,
+and prints the result line.  With --full rank 0 also measures, after the timed region and OUTSIDE the headline: the same
+steps as plain launches beside the graph replays, in-order dispatch, one launch per step, the update alone and the roofline
+of the headline kernel; the other BASELINE configurations at their per-GPU sizes and the kinematics producer
+(`other_configs`), the CPU reference path on the host cores (`cpu_baseline`, a thread sweep), and the parity of the headline
+batch against qpOASES with per-instance KKT / lexicographic evidence (`parity`).
 
 Prints ONE JSON line on rank 0.
 """
@@ -1138,6 +1141,25 @@ def sub_leaf(lf, lo, hi):
     return out
 
 
+DUMP_LIMIT_BYTES = 64 * 10 ** 6     # all of --dump-outputs' files together, .npy headers included
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """arrays (name -> per-instance rows, global instance order) as DIR/<name>.npy in float64.  Above `limit` bytes in all, a fixed
+    seeded sample of the instances is written instead, with its instance indices as sample_index.npy."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64) for k, v in arrays.items()}
+    rows = next(iter(arrays.values())).shape[0]
+    per_row = sum(8 * (v[0].size if v.ndim > 1 else 1) for v in arrays.values())
+    if rows * per_row > limit:
+        keep = (limit - 4096) // (per_row + 8)      # (+ the sample's indices; 4 KB for the headers)
+        idx = np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))
+        arrays = {k: v[idx] for k, v in arrays.items()}
+        arrays["sample_index"] = idx.astype(np.float64)
+    for k, v in arrays.items():
+        np.save(os.path.join(dirname, k + ".npy"), v)
+
+
 def self_launch(args):
     """`python bench.py --gpus N` without a launcher around it: re-execute under torch.distributed.run with N ranks on this
     node (rendezvous on 127.0.0.1, a free port); rank 0 of the children prints the JSON line.  The N = 1 path is untouched."""
@@ -1158,10 +1180,17 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch-per-gpu", type=int, default=4096)
     ap.add_argument("--config", default="C3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-other-configs", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, everything else the benchmark measures or checks: the stream-launch pass beside the graph "
+                         "replays, in-order dispatch, one launch per step, the update alone, the roofline, the other configurations, "
+                         "the CPU baseline and the parity against the reference (a plain run does none of it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path computed in its last step (every instance's dq and status, global instance "
+                         "order) as DIR/<name>.npy in float64")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no CPU baseline and no parity")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: no other configurations")
     ap.add_argument("--cpu-sweep", action="store_true",
-                    help="cpu_baseline with the 64-thread / all-cores points and the one-process-per-worker sweep (minutes of CPU)")
+                    help="with --full: cpu_baseline with the 64-thread / all-cores points and the one-process-per-worker sweep (minutes of CPU)")
     ap.add_argument("--details", default=os.path.join(ROOT, "bench_details.json"),
                     help="where the full record goes (protocol prose, sweeps, parity evidence, every sub-line's roofline block); "
                          "the stdout line is the compact form of it")
@@ -1263,17 +1292,33 @@ def main():
     cyc = PipelinedCycle(lanes, streams)
     st = stacks[0]
 
+    def outputs():
+        """what a caller of the timed path receives from its last step: every instance's dq and status in global instance order
+        (with a collective, what it delivered: all ranks' rows; otherwise the rank's own lanes)"""
+        if use_dist:
+            dq = np.empty((Bg, plan.n)); status = np.empty((Bg,))
+            for g, (a, b) in zip(gathers, spans):
+                gdq, gst = g.dq.double().cpu().numpy(), g.status.double().cpu().numpy()
+                for r in range(world):
+                    dq[r * Bl + a:r * Bl + b], status[r * Bl + a:r * Bl + b] = gdq[r * (b - a):(r + 1) * (b - a)], gst[r * (b - a):(r + 1) * (b - a)]
+        else:
+            dq = torch.cat([stj.dq[:b - a] for stj, (a, b) in zip(stacks, spans)]).double().cpu().numpy()
+            status = torch.cat([stj.status[:b - a] for stj, (a, b) in zip(stacks, spans)]).double().cpu().numpy()
+        return {"dq": dq, "status": status}
+
     # warm up first, then switch the event timing on for the timed steps only
     for _ in range(args.warmup):
         cyc.step()
     sync()
     # the steps of a lane as ONE HIP graph (opensot_amd.parallel.PipelinedCycle.capture): G steps per replay, G an even divisor
     # of --steps so that EXACTLY that many steps are timed (one graph per starting cycle of the rotation a replay can meet, so
-    # the replays follow the rotation like plain launches); the same steps submitted launch by launch are timed right after,
-    # with the HIP events that give the kernel's own duration
+    # the replays follow the rotation like plain launches); with --full the same steps submitted launch by launch are timed
+    # right after, with the HIP events that give the kernel's own duration
     graph_steps, graph_note, graph_elapsed, graph_host_ms, graph_diff, graph_launch_ms = 0, None, None, None, None, None
-    if not args.no_graph and not stub and streams is not None and (not use_dist or dist_graph):
-        cand = [g for g in range(4, 51, 2) if args.steps % g == 0]
+    last_outputs = None
+    cand = [g for g in range(4, 51, 2) if args.steps % g == 0]
+    try_graph = not args.no_graph and not stub and streams is not None and (not use_dist or dist_graph)
+    if try_graph:
         if cand:
             try:
                 cyc.capture(max(cand))
@@ -1282,6 +1327,8 @@ def main():
                 graph_elapsed = timed_steps(lambda: cyc.replay(timed=True), args.steps // graph_steps, 0, sync, dist if use_dist else None, device)
                 graph_launch_ms = cyc.replay_launch_ms()
                 graph_host_ms = 1e3 * getattr(timed_steps, "host_enqueue_s", 0.0) / args.steps
+                if args.dump_outputs:
+                    last_outputs = outputs()
                 g_dq = torch.cat([stj.dq[:b - a] for stj, (a, b) in zip(stacks, spans)]).clone()
                 g_ok = sum(int((stj.status[:b - a] == 0).sum().item()) for stj, (a, b) in zip(stacks, spans))
                 # one more rotation through plain launches ends on the same cycle: bit-identical results expected
@@ -1296,16 +1343,27 @@ def main():
                 graph_note, graph_elapsed = f"graph capture unavailable: {e}"[:300], None
         else:
             graph_note = "--steps has no even divisor in 4..20: launches submitted one by one"
-    for stj in stacks:
-        stj.set_timing(True, stride=4)     # every fourth launch of a lane is bracketed by HIP events on its stream
-    elapsed = timed_steps(cyc.step, args.steps, 0, sync, dist if use_dist else None, device)
-    host_enqueue_ms = 1e3 * getattr(timed_steps, "host_enqueue_s", 0.0) / args.steps
-    stream_elapsed = elapsed
+    if use_dist and try_graph and cand:
+        # every rank times the same passes: the graph replays count only where every rank could use them
+        used = torch.tensor([0.0 if graph_elapsed is None else 1.0], dtype=torch.float64, device=device)
+        dist.all_reduce(used, op=dist.ReduceOp.MIN)
+        if graph_elapsed is not None and used.item() == 0.0:
+            graph_note, graph_elapsed = "graph replay not usable on every rank: not used", None
+    # the same steps launch by launch: the headline where the graph form is not used, beside it with --full
+    stream_elapsed, kern_ms, launches = None, 0.0, 0
+    if graph_elapsed is None or args.full:
+        for stj in stacks:
+            stj.set_timing(True, stride=4)     # every fourth launch of a lane is bracketed by HIP events on its stream
+        elapsed = timed_steps(cyc.step, args.steps, 0, sync, dist if use_dist else None, device)
+        host_enqueue_ms = 1e3 * getattr(timed_steps, "host_enqueue_s", 0.0) / args.steps
+        stream_elapsed = elapsed
+        if graph_elapsed is None and args.dump_outputs:
+            last_outputs = outputs()
+        kt = [stj.kernel_time_ms() for stj in stacks]
+        launches = sum(c for _, c in kt)
+        kern_ms = sum(ms * c for ms, c in kt) / launches if launches else 0.0
     if graph_elapsed is not None:
         elapsed, host_enqueue_ms = graph_elapsed, graph_host_ms
-    kt = [stj.kernel_time_ms() for stj in stacks]
-    launches = sum(c for _, c in kt)
-    kern_ms = sum(ms * c for ms, c in kt) / launches if launches else 0.0
     ok = sum(int((stj.status[:b - a] == 0).sum().item()) for stj, (a, b) in zip(stacks, spans))
     all_ok, gather_diff = None, None
     if use_dist:
@@ -1316,46 +1374,46 @@ def main():
             off = sum(g.sizes[:rank])
             mine = g.dq[off:off + (b - a)]
             gather_diff = max(gather_diff, float((mine - stj.dq[:b - a]).abs().max().item()))
-    # the same kernel with plain in-order dispatch (reported beside the headline, never as the headline)
-    for stj in stacks:
-        stj.set_schedule(longest_first=False)
-    for _ in range(3):
-        cyc.step()
-    sync()
-    for stj in stacks:
-        stj.kernel_time_ms()
-    t1 = time.perf_counter()
-    for _ in range(10):
-        cyc.step()
-    sync()
-    inorder_elapsed = (time.perf_counter() - t1) / 10
-    ikt = [stj.kernel_time_ms() for stj in stacks]
-    inorder_kern_ms = sum(ms * c for ms, c in ikt) / max(1, sum(c for _, c in ikt))
-    for stj in stacks:
-        stj.set_schedule(longest_first=True)
-        stj.set_timing(False)
-    # one launch per step (no lanes), same steps: what the pipelining is worth, reported beside the headline
-    single_value = None
-    if S > 1 and not stub and not use_dist:
-        st1 = BatchedStack(plan, Bl, device=local_rank, want_levels=False)
-        devs1, A1 = [], []
-        for lf in leaves:
-            st1.A = [None if t is None else torch.empty_like(t) for t in st1.A]
-            devs1.append(st1.load_leaf(lf)); A1.append(st1.A)
-        one = ShardedCycle(st1, devs1, A1, Bl, None)
-        single_value = Bl * args.steps / timed_steps(one.step, args.steps, args.warmup, sync, None, device)
-        del one, st1, devs1, A1
-    update_ms = None
-    if not stub:
-        # the AutoStack::update equivalent on its own (SURVEY 8d asks for it beside the whole-step figure)
-        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        e0.record()
-        for i in range(20):
-            for stj, ln in zip(stacks, lanes):
-                stj.update(ln.dev_leaves[i % K])
-        e1.record()
+    inorder_elapsed, inorder_kern_ms, single_value, update_ms = None, None, None, None
+    if args.full:
+        # the same kernel with plain in-order dispatch (reported beside the headline, never as the headline)
+        for stj in stacks:
+            stj.set_schedule(longest_first=False)
+        for _ in range(3):
+            cyc.step()
         sync()
-        update_ms = e0.elapsed_time(e1) / 20
+        for stj in stacks:
+            stj.kernel_time_ms()
+        t1 = time.perf_counter()
+        for _ in range(10):
+            cyc.step()
+        sync()
+        inorder_elapsed = (time.perf_counter() - t1) / 10
+        ikt = [stj.kernel_time_ms() for stj in stacks]
+        inorder_kern_ms = sum(ms * c for ms, c in ikt) / max(1, sum(c for _, c in ikt))
+        for stj in stacks:
+            stj.set_schedule(longest_first=True)
+            stj.set_timing(False)
+        # one launch per step (no lanes), same steps: what the pipelining is worth, reported beside the headline
+        if S > 1 and not stub and not use_dist:
+            st1 = BatchedStack(plan, Bl, device=local_rank, want_levels=False)
+            devs1, A1 = [], []
+            for lf in leaves:
+                st1.A = [None if t is None else torch.empty_like(t) for t in st1.A]
+                devs1.append(st1.load_leaf(lf)); A1.append(st1.A)
+            one = ShardedCycle(st1, devs1, A1, Bl, None)
+            single_value = Bl * args.steps / timed_steps(one.step, args.steps, args.warmup, sync, None, device)
+            del one, st1, devs1, A1
+        if not stub:
+            # the AutoStack::update equivalent on its own (SURVEY 8d asks for it beside the whole-step figure)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            for i in range(20):
+                for stj, ln in zip(stacks, lanes):
+                    stj.update(ln.dev_leaves[i % K])
+            e1.record()
+            sync()
+            update_ms = e0.elapsed_time(e1) / 20
 
     if rank == 0:
         value = Bg * args.steps / elapsed
@@ -1379,11 +1437,12 @@ def main():
                        "rows_per_level": [plan.m(k) for k in range(plan.L)], "lanes_per_gpu": S,
                        "parallelism": f"instances sharded over {world} GPU(s), no data-path collective"},
             "solved_ok_rank0": f"{ok}/{Bl}",
-            "update_avg_ms_rank0": update_ms,
             "dispatch": {"mode": "longest-first by the previous cycle's active-set iteration counts "
-                                 "(osot_solver_set_schedule default; results are order-independent)",
-                         "in_order_value_rank0": Bl / inorder_elapsed, "in_order_avg_launch_ms": inorder_kern_ms},
+                                 "(osot_solver_set_schedule default; results are order-independent)"},
         }
+        if args.full:
+            out["update_avg_ms_rank0"] = update_ms
+            out["dispatch"].update(in_order_value_rank0=Bl / inorder_elapsed, in_order_avg_launch_ms=inorder_kern_ms)
         if stub:
             out["data"] = "STUB BACK-END (CPU tensors, gloo, no solver): launcher / sharding / gather check only, not a result"
         if single_value is not None:
@@ -1391,15 +1450,16 @@ def main():
         out["submission"] = {
             "mode": ("hip graph: %d steps of a lane per graph, one graph launch per lane and %d steps" % (graph_steps, graph_steps))
                     if graph_elapsed is not None else "one launch per lane and step on the lane's stream",
-            "stream_launch_value_rank0": Bl * args.steps / stream_elapsed,
-            "stream_launch_ms_per_step": 1e3 * stream_elapsed / args.steps,
             "graph_vs_stream_launch_max_abs_dq_diff": graph_diff,
             "note": graph_note or ("the timed region is EXACTLY --steps steps in both forms; roofline.avg_launch_ms is measured inside the "
                                    "graph pass, roofline.avg_launch_ms_stream_pass over the event-bracketed launches of the stream pass")}
+        if stream_elapsed is not None:
+            out["submission"].update(stream_launch_value_rank0=Bl * args.steps / stream_elapsed,
+                                     stream_launch_ms_per_step=1e3 * stream_elapsed / args.steps)
         if all_ok is not None:
             out["solved_ok_all_ranks"] = f"{all_ok}/{Bg}"
             out["gathered_vs_own_max_abs_dq_diff_rank0"] = gather_diff
-        if launches > 0 and kern_ms > 0 and not stub:
+        if args.full and launches > 0 and kern_ms > 0 and not stub:
             traffic, src = pmc_traffic([("osot_cycle_kernel<32, false, true>", Bl // S + 1, 1)])   # (+ the order workgroup)
             # S launches are in flight at a time (one per lane), each sharing the chip with the others: a launch's own duration is
             # not the time the chip needed for its instances.  The roofline figures therefore take the time of a whole STEP (all
@@ -1444,7 +1504,7 @@ def main():
             rh["achieved"] = rh["algorithmic_bytes_per_solve"] * Bl / ((step_ms if S > 1 else kern_ms) * 1e-3) / 1e9
             rh["frac"] = rh["achieved"] / rh["peak"]
             out["roofline"], out["roofline_hbm"] = rf, rh
-        if world == 1 and not args.no_other_configs and not stub:
+        if args.full and world == 1 and not args.no_other_configs and not stub:
             oc = {}
             for key, name, B, st_ in (("C2", "C2", 1024, 20), ("C4", "C4", 4096, 20), ("C5", "C5", 1024, 20),
                                       ("C5_B4096", "C5", 4096, 12)):   # (the last: config 5 beyond the shard size, four rounds of resident wavefronts)
@@ -1511,7 +1571,7 @@ def main():
                 except Exception as e:
                     oc[key] = {"error": str(e)}
             out["other_configs"] = oc
-        if not args.no_cpu_baseline and world == 1 and not stub:
+        if args.full and not args.no_cpu_baseline and world == 1 and not stub:
             ns = min(Bl, 4096)
             sample = {"B": ns, "A": [a[:ns] if a is not None else None for a in leaf["A"]],
                       "task": [[tuple(None if x is None else x[:ns] for x in t) for t in lev] for lev in leaf["task"]],
@@ -1537,6 +1597,8 @@ def main():
                 out["cpu_baseline"] = {"value": None, "unit": "solves/s", "cores": 0, "kind": "port",
                                        "sample": f"unavailable: {e}"}
         sys.stdout.flush()
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, last_outputs)
         # the full record: to a side file and to stderr; stdout carries the compact form only (the driver's capture is finite)
         full = json.dumps(out)
         try:

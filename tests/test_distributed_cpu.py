@@ -181,3 +181,38 @@ def test_bench_self_launches_two_ranks_on_the_stub_backend():
     assert out["n_gpus"] == 2 and out["steps"] == 3 and out["config"]["global_batch"] == 96
     assert len(out["config"]["workload"]) <= 300
     assert out["solved_ok_all_ranks"] == "96/96" and "STUB" in out["data"]
+
+
+def test_bench_dump_outputs_on_the_stub_backend(tmp_path):
+    """`bench.py --dump-outputs DIR`: the last timed step's dq and status of every instance, in global instance order, as float64
+    .npy files; the same arguments give the same files, and a world of two hands back rank 0's rows where a world of one has
+    them.  The result line's ms_per_step is the time of one of the --steps timed steps."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+
+    def run(gpus, name):
+        d = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", str(gpus), "--backend", "stub", "--steps", "3",
+                            "--warmup", "1", "--batch-per-gpu", "48", "--lanes", "2", "--dump-outputs", str(d),
+                            "--details", str(tmp_path / (name + ".json"))], capture_output=True, text=True, timeout=600, env=env, cwd=root)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out["steps"] == 3 and out["ms_per_step"] > 0.0
+        assert abs(out["value"] * out["ms_per_step"] - 1e3 * 48 * gpus) <= 1e-5 * out["value"] * out["ms_per_step"]
+        dq, status = np.load(d / "dq.npy"), np.load(d / "status.npy")
+        assert dq.dtype == np.float64 and status.dtype == np.float64
+        assert dq.shape == (48 * gpus, 32) and status.shape == (48 * gpus,)
+        assert np.isfinite(dq).all() and (status == 0).all()
+        return dq
+    one = run(1, "one")
+    np.testing.assert_array_equal(run(1, "again"), one)
+    two = run(2, "two")
+    np.testing.assert_array_equal(two[:48], one)
+    assert not np.array_equal(two[48:], one)

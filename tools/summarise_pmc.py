@@ -27,5 +27,5 @@ print(json.dumps({"kernel_source_sha": bench.kernel_source_sha(),
                   "correction": "MI355X_MICROARCH.md HBM section: FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports 1/2 of "
                                 "the bytes of a coalesced stream, so it is doubled; WRITE_SIZE taken as is; separate --pmc passes, "
                                 "--kernel-trace only; averages over the launches of a (kernel, grid) pair in `python bench.py "
-                                "--no-cpu-baseline --steps 10 --warmup 2`",
+                                "--full --no-cpu-baseline --steps 10 --warmup 2`",
                   "kernels": rows}, indent=1))
