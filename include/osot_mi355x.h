@@ -44,7 +44,8 @@ extern "C" {
 #define OSOT_MAX_VARS 64      /* one lane per variable        */
 #define OSOT_MAX_QP_VARS 128  /* the explicit-QP surface (osot_qp_solve_batch, osot_backend_*): 65 .. 128 variables run one
                                  256-thread workgroup per QP instead of one wavefront (round 6; cold start, no graph capture);
-                                 plans (osot_solver_create), nHQP / eHQP and the ADMM kernel stay at OSOT_MAX_VARS */
+                                 plans: osot_solver_create (the wavefront route) stays at OSOT_MAX_VARS, osot_solver_create_wide
+                                 takes up to OSOT_MAX_QP_VARS; nHQP / eHQP and the ADMM kernel stay at OSOT_MAX_VARS */
 
 /* error codes (the reference returns bool / throws std::runtime_error) */
 enum {
@@ -305,14 +306,36 @@ const char* osot_version(void);
 const char* osot_last_error(void);           /* thread-local text of the last failure */
 int osot_device_count(int* count);
 
-/* plan-derived sizes (host only, no GPU needed) */
+/* plan-derived sizes (host only, no GPU needed).
+ * osot_plan_validate: the WAVEFRONT route (osot_solver_create): 1 <= n <= OSOT_MAX_VARS, one wavefront per instance.
+ * osot_plan_validate_wide: the WORKGROUP route (osot_solver_create_wide): 1 <= n <= OSOT_MAX_QP_VARS with the same feature set
+ * (every task kind, implicit and stored Postural blocks, diagonal and dense weights, c vectors, sub-tasks of parents of at most
+ * 64 rows, body frames, gain matrices, both regularisation forms, every bound and row kind, global and task-local rows); the
+ * rows of all levels and the constraint rows together at most 2048 (OSOT_ERR_UNSUPPORTED beyond), and the row table must fit
+ * the LDS of a CU. */
 int osot_plan_validate(const osot_plan_desc* plan);
+int osot_plan_validate_wide(const osot_plan_desc* plan);
 int osot_plan_level_rows(const osot_plan_desc* plan, int level, int* m_total, int* m_stored);
 int osot_plan_constraint_rows(const osot_plan_desc* plan, int* nc);
 int osot_plan_stored_constraint_rows(const osot_plan_desc* plan, int* nc_stored);
 
 /* solver object: owns the per-plan device workspace for up to max_batch instances on `device` */
 int osot_solver_create(const osot_plan_desc* plan, int max_batch, int device, osot_solver** out);
+/* The same solver object for the WORKGROUP route (plans of 1 .. OSOT_MAX_QP_VARS variables; opensot_amd/csrc/osot_cascade_wide.h):
+ * the iHQP cascade runs one 256-thread workgroup per instance on the dual active-set solver of osot_qp_solve_batch's wide path, the
+ * grid capped at the workgroups the device holds at once, each with a slice of a workspace (2 n^2 doubles) allocated here, once:
+ * no allocation per call, so osot_cycle on a wide handle can be captured into a HIP graph.  On a wide handle:
+ *   osot_solver_destroy, osot_stack_update, osot_ihqp_solve, osot_solver_set_task_active, osot_solver_set_timing,
+ *   osot_solver_kernel_time_ms .... as on the wavefront route (the timing brackets the cascade launch);
+ *   osot_cycle ...................... TWO launches on the stream (osot_stack_update's kernel, then the cascade); results are
+ *                                     bit-identical to the two calls;
+ *   osot_solver_set_schedule, osot_solver_set_specialisation ... accepted, without effect (instances are dispatched in order);
+ *   osot_solver_resident_waves ...... the instances in flight: resident workgroups of the wide kernel (one instance each);
+ *   osot_nhqp_solve, osot_ehqp_solve, osot_control_cycle, osot_control_rollout, osot_solver_set_hotstart(s, 1),
+ *   osot_solver_profile_phases, osot_solver_resident_waves_nhqp ... OSOT_ERR_UNSUPPORTED with a reason.
+ * A level's status and accepted_slack follow the wavefront route's rules (round-off of the levels above: at most
+ * min(1e-6 * max(1, |bound|), 1e-5), status SOLVED). */
+int osot_solver_create_wide(const osot_plan_desc* plan, int max_batch, int device, osot_solver** out);
 int osot_solver_destroy(osot_solver* s);
 
 /* AutoStack::update() for B instances: leaf inputs -> b_k, w_k, merged box, constraint rows.

@@ -142,7 +142,7 @@ class KinBatch(C.Structure):
 
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
-    "osot_plan_validate", "osot_plan_level_rows", "osot_plan_constraint_rows",
+    "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
@@ -191,6 +191,8 @@ def lib():
     L.osot_last_error.restype = C.c_char_p
     L.osot_device_count.argtypes = [ip]
     L.osot_plan_validate.argtypes = [C.POINTER(PlanDesc)]
+    L.osot_plan_validate_wide.argtypes = [C.POINTER(PlanDesc)]   # the workgroup route: 1 <= n <= MAX_QP_VARS
+    L.osot_solver_create_wide.argtypes = [C.POINTER(PlanDesc), C.c_int, C.c_int, C.POINTER(vp)]
     L.osot_plan_level_rows.argtypes = [C.POINTER(PlanDesc), C.c_int, ip, ip]
     L.osot_plan_constraint_rows.argtypes = [C.POINTER(PlanDesc), ip]
     L.osot_plan_stored_constraint_rows.argtypes = [C.POINTER(PlanDesc), ip]

@@ -68,11 +68,14 @@ inline int plan_stored_constraint_rows(const osot_plan_desc* p, int* nc_stored) 
     return OSOT_OK;
 }
 
-inline int plan_validate(const osot_plan_desc* p, const char** why) {
+// wide = 0: the wavefront route (osot_plan_validate, osot_solver_create: n <= OSOT_MAX_VARS); 1: the workgroup route
+// (osot_plan_validate_wide, osot_solver_create_wide: n <= OSOT_MAX_QP_VARS, osot_cascade_wide.h) -- the same feature set
+inline int plan_validate(const osot_plan_desc* p, const char** why, int wide = 0) {
     static const char* ok = "";
     *why = ok;
     if (!p) { *why = "null plan"; return OSOT_ERR_INVALID; }
-    if (p->n < 1 || p->n > OSOT_MAX_VARS) { *why = "n out of range (1..64)"; return OSOT_ERR_INVALID; }
+    if (!wide && (p->n < 1 || p->n > OSOT_MAX_VARS)) { *why = "n out of range (1..64)"; return OSOT_ERR_INVALID; }
+    if (wide && (p->n < 1 || p->n > OSOT_MAX_QP_VARS)) { *why = "n out of range (1..128)"; return OSOT_ERR_INVALID; }
     if (p->n_levels < 1 || p->n_levels > OSOT_MAX_LEVELS) { *why = "n_levels out of range"; return OSOT_ERR_INVALID; }
     if (p->n_bounds < 0 || p->n_bounds > OSOT_MAX_BOUNDS) { *why = "n_bounds out of range"; return OSOT_ERR_INVALID; }
     if (p->n_rowblocks < 0 || p->n_rowblocks > OSOT_MAX_ROWBLOCKS) { *why = "n_rowblocks out of range"; return OSOT_ERR_INVALID; }
@@ -157,6 +160,12 @@ inline int plan_validate(const osot_plan_desc* p, const char** why) {
             *why = "unit-row block exceeds the variables"; return OSOT_ERR_INVALID; }
         if (rows_are_implicit(rb.kind) && rb.kind != OSOT_ROWS_UNIT_GENERIC && !(rb.dT * rb.p > 0.0)) { *why = "acceleration limits need dT*p > 0"; return OSOT_ERR_INVALID; }
         if (rb.only_level < 0 || rb.only_level > p->n_levels) { *why = "row block: only_level out of range (0..n_levels)"; return OSOT_ERR_INVALID; }
+    }
+    if (wide) {   // the workgroup solver's row limit (osot_qp_big.h: kMaxRows) holds the global rows and every level's optimality rows
+        int nc = 0, rows = 0;
+        plan_constraint_rows(p, &nc);
+        for (int k = 0; k < p->n_levels; ++k) for (int j = 0; j < p->level[k].n_tasks; ++j) rows += p->level[k].task[j].rows;
+        if (nc + rows > 2048) { *why = "wide route: more than 2048 constraint and task rows together"; return OSOT_ERR_UNSUPPORTED; }
     }
     return OSOT_OK;
 }

@@ -23,6 +23,7 @@
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
 #include "osot_qp_big.h"
+#include "osot_cascade_wide.h"
 
 using namespace osot;
 
@@ -112,7 +113,18 @@ struct osot_solver {
     int specialise = 1;         // osot_solver_set_specialisation: the BOX instantiation for plans without constraint rows
     int* d_hot = nullptr;    // [max_batch][n_levels][T] constraint codes, -1 = none (allocated when first switched on)
     int hot_T = 0;
+    // the workgroup route (osot_solver_create_wide, osot_cascade_wide.h): one 256-thread workgroup per instance
+    int wide = 0;
+    double* d_work = nullptr;   // [wide_grid][2][n][n]: L and J of every resident workgroup, allocated once
+    int wide_grid = 0;          // workgroups of a launch: the resident ones, at most max_batch
+    size_t wide_lds = 0;
 };
+
+// entries that the workgroup route does not carry
+static int refuse_wide(const osot_solver* s, const char* what) {
+    if (s && s->wide) return fail(OSOT_ERR_UNSUPPORTED, std::string(what) + " is not available on the wide route (osot_solver_create_wide)");
+    return OSOT_OK;
+}
 
 extern "C" {
 
@@ -180,6 +192,16 @@ int osot_plan_validate(const osot_plan_desc* plan) {
     const char* why;
     int rc = plan_validate(plan, &why);
     if (rc != OSOT_OK) return fail(rc, why);
+    return OSOT_OK;
+}
+int osot_plan_validate_wide(const osot_plan_desc* plan) {
+    const char* why;
+    int rc = plan_validate(plan, &why, 1);
+    if (rc != OSOT_OK) return fail(rc, why);
+    if (wide::shared_bytes(plan->n, [&] { int nc = 0, rows = 0; plan_constraint_rows(plan, &nc);
+                                          for (int k = 0; k + 1 < plan->n_levels; ++k) { int m = 0; plan_level_rows(plan, k, &m, nullptr); rows += m; }
+                                          return nc + rows; }()) > 160 * 1024)
+        return fail(OSOT_ERR_UNSUPPORTED, "wide route: the row table of this plan does not fit the 160 KiB LDS of a CU");
     return OSOT_OK;
 }
 int osot_plan_level_rows(const osot_plan_desc* plan, int level, int* m_total, int* m_stored) {
@@ -278,9 +300,50 @@ int osot_solver_create(const osot_plan_desc* plan, int max_batch, int device, os
     return OSOT_OK;
 }
 
+int osot_solver_create_wide(const osot_plan_desc* plan, int max_batch, int device, osot_solver** out) {
+    if (!out) return fail(OSOT_ERR_INVALID, "null out");
+    *out = nullptr;
+    int rc = osot_plan_validate_wide(plan);
+    if (rc != OSOT_OK) return rc;
+    if (max_batch < 1) return fail(OSOT_ERR_INVALID, "max_batch < 1");
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    wide::Plan P;
+    wide::make_plan(*plan, nullptr, nullptr, P);
+    const size_t lds = wide::shared_bytes(P.n, P.nrows);
+    rc = ensure_lds(osot_cascade_wide_kernel, lds);
+    if (rc != OSOT_OK) return rc;
+    int per_cu = 0, cus = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_cascade_wide_kernel, 256, lds));
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+    if (per_cu < 1 || cus < 1) return fail(OSOT_ERR_UNSUPPORTED, "the wide cascade kernel does not fit a CU for this plan");
+    osot_solver* s = new osot_solver();
+    s->plan = *plan;
+    s->max_batch = max_batch;
+    s->device = device;
+    s->timing = false;
+    s->wide = 1;
+    s->wide_lds = lds;
+    s->slots = per_cu * cus;
+    s->wide_grid = max_batch < s->slots ? max_batch : s->slots;
+    std::memset(s->task_active, 1, sizeof(s->task_active));
+    make_update_plan(*plan, s->h_uplan);
+    if (hipMalloc(&s->d_work, sizeof(double) * 2 * (size_t)P.n * P.n * (size_t)s->wide_grid) != hipSuccess ||
+        hipMalloc(&s->d_uplan, sizeof(DevUpdatePlan)) != hipSuccess ||
+        hipMemcpy(s->d_uplan, &s->h_uplan, sizeof(DevUpdatePlan), hipMemcpyHostToDevice) != hipSuccess) {
+        if (s->d_work) hipFree(s->d_work);
+        if (s->d_uplan) hipFree(s->d_uplan);
+        delete s;
+        return fail(OSOT_ERR_HIP, "device allocation for the solver failed");
+    }
+    *out = s;
+    return OSOT_OK;
+}
+
 int osot_solver_destroy(osot_solver* s) {
     if (!s) return OSOT_OK;
     DeviceGuard guard(s->device);
+    if (s->d_work) hipFree(s->d_work);
     for (auto& p : s->events) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     for (auto& p : s->pool) { hipEventDestroy(p.first); hipEventDestroy(p.second); }
     if (s->d_cost) hipFree(s->d_cost);
@@ -313,6 +376,7 @@ int osot_solver_set_specialisation(osot_solver* s, int enabled) {
 
 int osot_solver_set_hotstart(osot_solver* s, int enabled) {
     if (!s) return fail(OSOT_ERR_INVALID, "null solver");
+    if (enabled && s->wide) return refuse_wide(s, "hot start");
     DeviceGuard guard(s->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
     if (enabled) {
@@ -364,6 +428,7 @@ int osot_solver_set_timing(osot_solver* s, int enabled) {
 
 int osot_ehqp_solve(osot_solver* s, const osot_qp_batch* b, double sigma_min, void* hip_stream) {
     if (!s || !b) return fail(OSOT_ERR_INVALID, "null solver/batch");
+    if (s->wide) return refuse_wide(s, "the eHQP front-end");
     if (b->B < 0 || b->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
     if (b->B == 0) return OSOT_OK;
     if (!b->dq || !b->status) return fail(OSOT_ERR_INVALID, "dq/status output is null");
@@ -390,6 +455,7 @@ int osot_ehqp_solve(osot_solver* s, const osot_qp_batch* b, double sigma_min, vo
 
 int osot_nhqp_solve(osot_solver* s, const osot_qp_batch* b, const osot_nhqp_options* opt, void* hip_stream) {
     if (!s || !b) return fail(OSOT_ERR_INVALID, "null solver/batch");
+    if (s->wide) return refuse_wide(s, "the nHQP front-end");
     if (b->B < 0 || b->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
     if (b->B == 0) return OSOT_OK;
     if (!b->dq || !b->status) return fail(OSOT_ERR_INVALID, "dq/status output is null");
@@ -468,6 +534,7 @@ int osot_solver_resident_waves(osot_solver* s, int* waves) {
 // resident wavefronts sets the round (static 25 KB of LDS at n <= 32: six per CU; the 64-column and wide kernels by the plan's sizes)
 int osot_solver_resident_waves_nhqp(osot_solver* s, const osot_nhqp_options* opt, int* waves) {
     if (!s || !waves) return fail(OSOT_ERR_INVALID, "null argument");
+    if (s->wide) return refuse_wide(s, "the nHQP front-end");
     DeviceGuard guard(s->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
     const osot_plan_desc& pl = s->plan;
@@ -539,7 +606,63 @@ int osot_cycle(osot_solver* s, const osot_leaf_batch* leaf, const osot_assembled
 
 int osot_solver_profile_phases(osot_solver* s, const osot_qp_batch* b, long long* cycles, void* hip_stream) {
     if (!cycles) return fail(OSOT_ERR_INVALID, "null cycles");
+    if (s && s->wide) return refuse_wide(s, "phase profiling");
     return ihqp_launch(s, b, hip_stream, cycles);
+}
+
+// the workgroup route: osot_ihqp_solve, and osot_cycle as TWO launches on the stream (osot_update_kernel, then the cascade)
+static int wide_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control) {
+    if (prof) return refuse_wide(s, "phase profiling");
+    if (control) return refuse_wide(s, "the fused control cycle / rollout");
+    const osot_plan_desc& pl = s->plan;
+    wide::Plan P;
+    wide::make_plan(pl, b->level_active, s->any_inactive ? s->task_active : nullptr, P);
+    wide::Batch D;
+    std::memset(&D, 0, sizeof(D));
+    D.B = b->B;
+    for (int k = 0; k < pl.n_levels; ++k) {
+        if (P.ma[k] > 0 && !b->A[k]) return fail(OSOT_ERR_INVALID, "A[k] is null for a level with stored rows");
+        if (!b->b[k]) return fail(OSOT_ERR_INVALID, "b[k] is null");
+        D.A[k] = b->A[k]; D.b[k] = b->b[k]; D.w[k] = b->w[k]; D.c[k] = b->c[k];
+        if (s->h_uplan.dense_level[k]) {
+            if (!b->WA[k] || !b->Wb[k]) return fail(OSOT_ERR_INVALID, "level has a non-diagonal weight but WA[k] / Wb[k] is null");
+            D.WA[k] = b->WA[k]; D.Wb[k] = b->Wb[k];
+        }
+    }
+    if (P.nc > 0 && (!b->lo || !b->up)) return fail(OSOT_ERR_INVALID, "plan has constraint rows but lo/up is null");
+    if (P.nc_stored > 0 && !b->C) return fail(OSOT_ERR_INVALID, "plan has stored constraint rows but C is null");
+    if (pl.n_bounds > 0 && (!b->l || !b->u)) return fail(OSOT_ERR_INVALID, "plan has bounds but l/u is null");
+    if (!b->dq || !b->status) return fail(OSOT_ERR_INVALID, "dq/status output is null");
+    if (pl.has_regularisation && !b->b_reg) return fail(OSOT_ERR_INVALID, "plan has a regularisation task but b_reg is null");
+    if (pl.has_regularisation && pl.regularisation_dense && !b->A_reg)
+        return fail(OSOT_ERR_INVALID, "the regularisation task has a stored Jacobian but A_reg is null");
+    D.C = P.nc_stored ? b->C : nullptr; D.lo = b->lo; D.up = b->up;
+    D.l = pl.n_bounds ? b->l : nullptr; D.u = pl.n_bounds ? b->u : nullptr;
+    D.b_reg = pl.has_regularisation ? b->b_reg : nullptr;
+    D.A_reg = (pl.has_regularisation && pl.regularisation_dense) ? b->A_reg : nullptr;
+    D.dq = b->dq; D.x_levels = b->x_levels; D.accepted_slack = b->accepted_slack;
+    D.status = b->status; D.iterations = b->iterations;
+    D.work = s->d_work;
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (fused) {
+        hipLaunchKernelGGL(osot_update_kernel, dim3((unsigned)b->B), dim3(64), 0, st, *fused);
+        HIP_TRY(hipGetLastError());
+    }
+    std::pair<hipEvent_t, hipEvent_t> ev;
+    const bool timed = s->timing && (s->timing_count++ % s->timing_stride) == 0;
+    if (timed) {
+        if (!s->pool.empty()) { ev = s->pool.back(); s->pool.pop_back(); }
+        else { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
+        HIP_TRY(hipEventRecord(ev.first, st));
+    }
+    const unsigned grid = (unsigned)(b->B < s->wide_grid ? b->B : s->wide_grid);
+    hipLaunchKernelGGL(osot_cascade_wide_kernel, dim3(grid), dim3(256), s->wide_lds, st, P, D);
+    HIP_TRY(hipGetLastError());
+    if (timed) {
+        HIP_TRY(hipEventRecord(ev.second, st));
+        s->events.push_back(ev);
+    }
+    return OSOT_OK;
 }
 
 static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control) {
@@ -548,6 +671,7 @@ static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
     if (b->B == 0) return OSOT_OK;   // empty batch: nothing to do
     DeviceGuard guard(s->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    if (s->wide) return wide_launch(s, b, hip_stream, prof, fused, control);
     const osot_plan_desc& pl = s->plan;
     DevPlan P; int T; size_t lds;
     make_dev_plan(pl, b->level_active, P, T, lds, s->any_inactive ? s->task_active : nullptr);
@@ -1141,6 +1265,7 @@ int osot_control_cycle(osot_solver* s, osot_kin* k, const osot_kin_batch* kb, co
 
 int osot_control_rollout(osot_solver* s, osot_kin* k, const osot_kin_batch* kb, const osot_leaf_batch* leaf, const osot_assembled_out* out,
                          const osot_qp_batch* b, double* q_integrate, int steps, double* dq_steps, int* status_steps, void* hip_stream) {
+    if (s && s->wide) return refuse_wide(s, "the fused control cycle / rollout");
     if (steps < 1) return fail(OSOT_ERR_INVALID, "a rollout has at least one step");
     if (steps > 1 && !q_integrate) return fail(OSOT_ERR_INVALID, "a rollout of several steps integrates q (q_integrate is null: every step would solve the same problem)");
     return control_launch(s, k, kb, leaf, out, b, q_integrate, steps, dq_steps, status_steps, hip_stream);
@@ -1149,6 +1274,7 @@ int osot_control_rollout(osot_solver* s, osot_kin* k, const osot_kin_batch* kb, 
 static int control_launch(osot_solver* s, osot_kin* k, const osot_kin_batch* kb, const osot_leaf_batch* leaf, const osot_assembled_out* out,
                           const osot_qp_batch* b, double* q_integrate, int steps, double* dq_steps, int* status_steps, void* hip_stream) {
     if (!s || !k || !kb || !leaf || !out || !b) return fail(OSOT_ERR_INVALID, "null argument");
+    if (s->wide) return refuse_wide(s, "the fused control cycle / rollout");
     if (leaf->B != b->B || kb->B != b->B) return fail(OSOT_ERR_INVALID, "kinematics batch, leaf batch and qp batch disagree on B");
     if (leaf->B < 0 || leaf->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
     if (leaf->B == 0) return OSOT_OK;

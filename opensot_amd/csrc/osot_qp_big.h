@@ -39,15 +39,51 @@ enum { ST_SOLVED = 0, ST_INFEASIBLE = 1, ST_MAX_ITER = 2, ST_NOT_PD = 3 };   // 
 struct Args {                         // one instance
     int n, nc, max_iter;
     double eps;
-    const double *H, *g, *A, *lA, *uA, *l, *u;   // l / u null: no box
+    const double *H, *g, *A, *lA, *uA, *l, *u;   // l / u null: no box.  H may be Lw itself (built in place by the caller)
     double* x;
     int* status;
     int* iters;                       // may be null
     double* Lw;                       // workspace [n][n]: H + eps I -> its Cholesky factor (lower triangle)
     double* J;                        // workspace [n][n]: J = L^-T, rotated / reflected as the working set changes
+    // cascade switch (osot_cascade_wide.h; the explicit-QP path leaves it off and keeps its statuses): a dependent equality that is
+    // inconsistent, or a violated constraint with no direction left and no multiplier to trade, is accepted as round-off of the levels
+    // above when the violation is at most min(kSlackRel max(1, |bound|), kSlackCap); the largest one goes to *slack (thread 0)
+    // With the switch on, the rest of the wavefront cascade's rule (osot_qp_core.h, gi_inequalities) comes along: an accepted bound or
+    // row is RELAXED by 1.001 x the violation for the rest of the instance's cascade (lmut / umut: the box the cascade hands in as l / u;
+    // rows: Rows::relax), so that the levels below accept the same point; a violation of at most kSpanAccept with its normal in the span
+    // of the working set is accepted ahead of a dual exchange; and up to kRefineMax times per level the round-off of the ITERATE is taken
+    // out first (x += J1 y with R'y = the working set's residuals) before a violation up to kSlackRel is accepted.
+    bool accept_slack = false;
+    double* slack = nullptr;
+    double *lmut = nullptr, *umut = nullptr;
 };
-enum { SI_IQ = 0, SI_ME, SI_IP, SI_SIDE, SI_ACT, SI_L, SI_ST, SI_ITERS, SI_DONE, SI_COUNT = 16 };
-enum { SD_T = 0, SD_ND2, SD_DD, SD_ALPHA, SD_BETA, SD_SIP, SD_PIV, SD_BND, SD_COUNT = 16 };
+constexpr double kSlackRel = 1.0e-6;  // (osot_qp_core.h: kSlackTol, kSlackCap, kSpanAccept, kRefineFloor, kRefineMax)
+constexpr double kSlackCap = 1.0e-5;
+constexpr double kSpanAccept = 1.0e-8;
+constexpr double kRefineFloor = 1.0e-9;
+constexpr int kRefineMax = 2;
+constexpr double kDepFloor2 = 1.0e-13;   // second dependence test of the cascade, where |d2|^2 <= 1e-12 |d|^2 (osot_qp_core.h: kDepFloor2)
+
+// The constraint rows as the solver sees them.  DenseRows: the explicit QP's A [nc][n] with lA <= A x <= uA.  A row source must
+// give the clamped bounds, a'x, and either the row's n coefficients or the variable of a unit row e_col (osot_cascade_wide.h: rows
+// described by a table, optimality rows taken relative to the previous level's solution).
+struct DenseRows {
+    const double *A, *lA, *uA;
+    int n;
+    OSOT_BIG_FN double lo(int r) const;
+    OSOT_BIG_FN double up(int r) const;
+    OSOT_BIG_FN int unit(int) const { return -1; }
+    OSOT_BIG_FN const double* row(int r) const { return A + (size_t)r * n; }
+    OSOT_BIG_FN void relax(int, int, double) const {}   // (the explicit QP never accepts a violation)
+    OSOT_BIG_FN double dot(int r, const double* x) const {
+        const double* ar = A + (size_t)r * n;
+        double acc = 0.0;
+        for (int i = 0; i < n; ++i) acc += ar[i] * x[i];
+        return acc;
+    }
+};
+enum { SI_IQ = 0, SI_ME, SI_IP, SI_SIDE, SI_ACT, SI_L, SI_ST, SI_ITERS, SI_DONE, SI_REFINE, SI_COUNT = 16 };
+enum { SD_T = 0, SD_ND2, SD_DD, SD_ALPHA, SD_BETA, SD_SIP, SD_PIV, SD_BND, SD_SLACK, SD_COUNT = 16 };
 struct Shared {                       // LDS on the device, heap on the host
     double* R;                        // packed upper triangle of the working set's factor: R(i, j) at j (j + 1) / 2 + i, i <= j
     double *x, *np, *d, *z, *r, *e;   // [n] each: iterate, normal, d = J'n, z = J2 d2, r = R^-1 d1, scratch
@@ -86,12 +122,14 @@ OSOT_BIG_FN Shared carve(void* base, int n, int nc) {
 
 OSOT_BIG_FN double clamp_inf(double v) { return v >= kInf ? kInf : (v <= -kInf ? -kInf : v); }
 OSOT_BIG_FN int ridx(int i, int j) { return ((j * (j + 1)) >> 1) + i; }
+OSOT_BIG_FN double DenseRows::lo(int r) const { return clamp_inf(lA[r]); }
+OSOT_BIG_FN double DenseRows::up(int r) const { return clamp_inf(uA[r]); }
 
 #define OSOT_BIG_FOR(i, N) for (int i = tm.tid; i < (N); i += tm.nt)
 
 // Team: { int tid, nt; void sync() const; }  -- every thread of the team calls solve() with the same arguments
-template <class Team>
-OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
+template <class Team, class Rows>
+OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Rows& rows) {
     const int n = a.n, nc = a.nc;
     const bool t0 = tm.tid == 0;
     const bool has_box = a.l != nullptr;
@@ -102,12 +140,12 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
     OSOT_BIG_FOR(e2, n * n) { const int i = e2 / n, j = e2 - i * n; L[e2] = a.H[e2] + ((i == j) ? a.eps : 0.0); }
     OSOT_BIG_FOR(i, n) { s.bstate[i] = 0; s.x[i] = 0.0; s.u[i] = 0.0; s.aset[i] = -1; s.aside[i] = 0; s.d[i] = -a.g[i]; }
     OSOT_BIG_FOR(r, nc) s.rstate[r] = 0;
-    if (t0) { s.si[SI_IQ] = 0; s.si[SI_ME] = 0; s.si[SI_ST] = ST_SOLVED; s.si[SI_ITERS] = 0; s.si[SI_DONE] = 0; s.u[n] = 0.0; }
+    if (t0) { s.si[SI_IQ] = 0; s.si[SI_ME] = 0; s.si[SI_ST] = ST_SOLVED; s.si[SI_ITERS] = 0; s.si[SI_DONE] = 0; s.si[SI_REFINE] = kRefineMax; s.u[n] = 0.0; s.sc[SD_SLACK] = 0.0; }
     tm.sync();
     auto finish = [&]() {              // (called by every thread, behind a barrier)
         const int st = s.si[SI_ST];
         OSOT_BIG_FOR(i, n) a.x[i] = (st == ST_SOLVED) ? s.x[i] : 0.0;
-        if (t0) { *a.status = st; if (a.iters) *a.iters = s.si[SI_ITERS]; }
+        if (t0) { *a.status = st; if (a.iters) *a.iters = s.si[SI_ITERS]; if (a.slack) *a.slack = fmax(*a.slack, s.sc[SD_SLACK]); }
         tm.sync();
     };
     // ---- Cholesky of H + eps I, right-looking, in place (lower triangle of L)
@@ -151,10 +189,11 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
     // d = J'n for the constraint (code, side), |d|^2 and |d2|^2, z = J2 d2.  Ends behind a barrier.
     auto compute_d = [&](int code, int side) {
         const int iq = s.si[SI_IQ];
-        if (code < n) {
-            OSOT_BIG_FOR(j, n) s.d[j] = side * J[code * n + j];
+        const int ucol = (code < n) ? code : rows.unit(code - n);
+        if (ucol >= 0) {
+            OSOT_BIG_FOR(j, n) s.d[j] = side * J[ucol * n + j];
         } else {
-            const double* ar = a.A + (size_t)(code - n) * n;
+            const double* ar = rows.row(code - n);
             OSOT_BIG_FOR(i, n) s.np[i] = side * ar[i];
             tm.sync();
             OSOT_BIG_FOR(j, n) { double acc = 0.0; for (int i = 0; i < n; ++i) acc += J[i * n + j] * s.np[i]; s.d[j] = acc; }
@@ -167,6 +206,28 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
         }
         OSOT_BIG_FOR(i, n) { double acc = 0.0; const double* row = J + (size_t)i * n; for (int j = iq; j < n; ++j) acc += row[j] * s.d[j]; s.z[i] = acc; }
         tm.sync();
+        // cascade: a normal at 1e-6 of the span of the working set is a direction on paper only -- taking it puts |d2| on the diagonal
+        // of R and moves x by violation / |d2|.  Per FREE column c of J: d_c^2 / (|J_c|^2 |n|^2) = cos^2 of its angle with the normal;
+        // no usable angle with any of them: dependent (osot_qp_core.h: direction_is_independent)
+        if (a.accept_slack && !(s.sc[SD_ND2] > 1.0e-12 * s.sc[SD_DD]) && s.sc[SD_ND2] > kDep2 * s.sc[SD_DD]) {
+            OSOT_BIG_FOR(c, n) {
+                double cos2 = 0.0;
+                if (c >= iq) {
+                    double cn = 0.0;
+                    for (int i = 0; i < n; ++i) { const double v = J[(size_t)i * n + c]; cn += v * v; }
+                    cos2 = (cn > 0.0) ? s.d[c] * s.d[c] / cn : 0.0;
+                }
+                s.e[c] = cos2;
+            }
+            tm.sync();
+            if (t0) {
+                double best = 0.0, nn = 1.0;
+                for (int c = iq; c < n; ++c) best = fmax(best, s.e[c]);
+                if (ucol < 0) { nn = 0.0; for (int i = 0; i < n; ++i) nn += s.np[i] * s.np[i]; }
+                if (!(best > kDepFloor2 * nn)) s.sc[SD_ND2] = 0.0;
+            }
+            tm.sync();
+        }
     };
     // the constraint whose d, z are current enters the working set at position iq: one Householder reflection of J2.  Ends behind a barrier.
     auto add_constraint = [&](int code, int side) {
@@ -197,6 +258,7 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
     // by column through a scratch vector: the packed storage has no room for the sub-diagonal), the same rotations on the columns of J.
     auto drop_constraint = [&](int l) {
         const int iq = s.si[SI_IQ];
+        tm.sync();                                       // (everybody has read iq before thread 0 moves it)
         if (t0) {
             const int code = s.aset[l];
             if (code < n) s.bstate[code] = 0; else s.rstate[code - n] = 0;
@@ -233,14 +295,21 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
 
     // ---- equality rows first (lA == uA after the clamp): a signed step onto each, no multipliers, never dropped
     for (int r = 0; r < nc; ++r) {
-        const double lo = clamp_inf(a.lA[r]), up = clamp_inf(a.uA[r]);
+        const double lo = rows.lo(r), up = rows.up(r);
         if (!(lo == up)) continue;
         tm.sync();                                       // (the scalars of the previous row have been read by everybody)
-        if (t0) { double acc = 0.0; const double* ar = a.A + (size_t)r * n; for (int i = 0; i < n; ++i) acc += ar[i] * s.x[i]; s.sc[SD_SIP] = acc - lo; s.rstate[r] = 3; }
+        if (t0) { s.sc[SD_SIP] = rows.dot(r, s.x) - lo; s.rstate[r] = 3; }
         compute_d(n + r, +1);
         const double nd2 = s.sc[SD_ND2], dd = s.sc[SD_DD], sip = s.sc[SD_SIP];
         if (!(nd2 > kDep2 * dd)) {                       // a combination of the rows already in
-            if (fabs(sip) > kEq * fmax(1.0, fabs(lo))) { tm.sync(); if (t0) s.si[SI_ST] = ST_INFEASIBLE; tm.sync(); finish(); return; }
+            if (fabs(sip) > kEq * fmax(1.0, fabs(lo))) {
+                if (a.accept_slack && fabs(sip) <= fmin(kSlackRel * fmax(1.0, fabs(lo)), kSlackCap)) {   // round-off of the levels above
+                    tm.sync();
+                    if (t0) s.sc[SD_SLACK] = fmax(s.sc[SD_SLACK], fabs(sip));
+                    continue;
+                }
+                tm.sync(); if (t0) s.si[SI_ST] = ST_INFEASIBLE; tm.sync(); finish(); return;
+            }
             continue;                                    // redundant and consistent
         }
         const double t = -sip / nd2;
@@ -268,11 +337,9 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
         OSOT_BIG_FOR(r, nc) {
             double v = 0.0; int sd = 0;
             if (s.rstate[r] == 0) {
-                const double lo = clamp_inf(a.lA[r]), up = clamp_inf(a.uA[r]);
+                const double lo = rows.lo(r), up = rows.up(r);
                 if (lo > -kInf || up < kInf) {
-                    const double* ar = a.A + (size_t)r * n;
-                    double ax = 0.0;
-                    for (int i = 0; i < n; ++i) ax += ar[i] * s.x[i];
+                    const double ax = rows.dot(r, s.x);
                     if (lo > -kInf) { const double vi = lo - ax; if (vi > kViol * fmax(1.0, fabs(lo)) && vi > v) { v = vi; sd = +1; } }
                     if (up < kInf) { const double vi = ax - up; if (vi > kViol * fmax(1.0, fabs(up)) && vi > v) { v = vi; sd = -1; } }
                 }
@@ -287,7 +354,7 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
             else {
                 const int sd = s.cside[ip];
                 s.si[SI_IP] = ip; s.si[SI_SIDE] = sd; s.sc[SD_SIP] = -best;
-                s.sc[SD_BND] = (ip < n) ? ((sd > 0) ? clamp_inf(a.l[ip]) : clamp_inf(a.u[ip])) : ((sd > 0) ? clamp_inf(a.lA[ip - n]) : clamp_inf(a.uA[ip - n]));
+                s.sc[SD_BND] = (ip < n) ? ((sd > 0) ? clamp_inf(a.l[ip]) : clamp_inf(a.u[ip])) : ((sd > 0) ? rows.lo(ip - n) : rows.up(ip - n));
                 s.u[s.si[SI_IQ]] = 0.0;
             }
         }
@@ -312,14 +379,43 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
                 const double nd2 = s.sc[SD_ND2], dd = s.sc[SD_DD], sip = s.sc[SD_SIP];
                 const bool has_dir = nd2 > kDep2 * dd;
                 const double t2 = has_dir ? -sip / nd2 : INFINITY;
-                int act; double t;
-                if (!(t1 < INFINITY) && !(t2 < INFINITY)) { act = 0; t = 0.0; }          // no step at all: infeasible
+                int act; double t = 0.0;
+                const double viol = -sip, bmag = fmax(1.0, fabs(s.sc[SD_BND]));
+                const bool refine = a.accept_slack && s.si[SI_REFINE] > 0;
+                if (a.accept_slack && !has_dir && t1 < INFINITY && viol <= kSpanAccept * bmag) act = 5;     // round-off ahead of an exchange: accept
+                else if (refine && !has_dir && t1 < INFINITY && viol <= kSlackRel * bmag) act = 6;          // ... or refine the iterate first
+                else if (!(t1 < INFINITY) && !(t2 < INFINITY)) {                                           // no step at all: infeasible, or
+                    act = 0;                                                                                // round-off of the levels above
+                    if (a.accept_slack && viol <= fmin(kSlackRel * bmag, kSlackCap)) act = (refine && viol > kRefineFloor * bmag) ? 6 : 5;
+                }
                 else if (t2 <= t1) { act = 2; t = t2; }                                    // full step: ip enters
                 else if (!has_dir) { act = 1; t = t1; }                                    // dual step only: l leaves
                 else { act = 3; t = t1; }                                                  // partial step: l leaves
-                if (act != 0) {
+                if (act >= 1 && act <= 3) {
                     for (int k = 0; k < iq; ++k) s.u[k] -= t * s.r[k];
                     s.u[iq] += t;
+                }
+                if (act == 5) {                                  // accepted: relaxed for the rest of the cascade, reported
+                    const double rx = 1.001 * viol;
+                    if (ip < n) { if (side > 0) a.lmut[ip] -= rx; else a.umut[ip] += rx; }
+                    else rows.relax(ip - n, side, rx);
+                    s.sc[SD_SLACK] = fmax(s.sc[SD_SLACK], viol);
+                }
+                if (act == 6) {                                  // refinement: residuals of the working set, R'y = rho into s.r
+                    s.si[SI_REFINE] -= 1;
+                    for (int q = 0; q < iq; ++q) {
+                        const int code = s.aset[q], sd = s.aside[q];
+                        double rq;
+                        if (code < n) rq = (sd > 0) ? (clamp_inf(a.l[code]) - s.x[code]) : (s.x[code] - clamp_inf(a.u[code]));
+                        else {
+                            const int r = code - n;
+                            const double ax = rows.dot(r, s.x);
+                            rq = (s.rstate[r] == 3 || sd > 0) ? (rows.lo(r) - ax) : (ax - rows.up(r));
+                        }
+                        double acc = rq;
+                        for (int i = 0; i < q; ++i) acc -= Rp[ridx(i, q)] * s.r[i];
+                        s.r[q] = acc / Rp[ridx(q, q)];
+                    }
                 }
                 if (++s.si[SI_ITERS] > a.max_iter) act = 4;
                 s.si[SI_ACT] = act; s.si[SI_L] = l; s.sc[SD_T] = t;
@@ -327,6 +423,13 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
             tm.sync();
             const int act = s.si[SI_ACT];
             const double t = s.sc[SD_T];
+            if (act == 5) break;                                 // (the scan goes on)
+            if (act == 6) {                                      // x += J1 y, then scan again
+                const int iq = s.si[SI_IQ];
+                OSOT_BIG_FOR(i, n) { double dx = 0.0; const double* row = J + (size_t)i * n; for (int j = 0; j < iq; ++j) dx += row[j] * s.r[j]; s.x[i] += dx; }
+                tm.sync();
+                break;
+            }
             if (act == 0 || act == 4) { if (t0) s.si[SI_ST] = (act == 0) ? ST_INFEASIBLE : ST_MAX_ITER; tm.sync(); finish(); return; }
             if (act >= 2) { OSOT_BIG_FOR(i, n) s.x[i] += t * s.z[i]; }
             tm.sync();
@@ -336,7 +439,7 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
                 if (t0) {
                     double ax;
                     if (ip < n) ax = s.x[ip];
-                    else { ax = 0.0; const double* ar = a.A + (size_t)(ip - n) * n; for (int i = 0; i < n; ++i) ax += ar[i] * s.x[i]; }
+                    else ax = rows.dot(ip - n, s.x);
                     s.sc[SD_SIP] = side * (ax - s.sc[SD_BND]);
                 }
                 tm.sync();
@@ -345,6 +448,9 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) {
     }
     finish();
 }
+// the explicit QP: dense rows A [nc][n]
+template <class Team>
+OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) { solve(tm, a, s, DenseRows{a.A, a.lA, a.uA, a.n}); }
 
 }  // namespace big
 

@@ -157,7 +157,8 @@ class StackPlan:
         return sum(r.rows for r in self.rowblocks[:j])
 
     def validate(self):
-        assert 1 <= self.n <= abi.MAX_VARS
+        # up to MAX_VARS on the wavefront route, up to MAX_QP_VARS on the workgroup route (BatchedStack(route="wide"))
+        assert 1 <= self.n <= abi.MAX_QP_VARS
         assert 1 <= self.L <= abi.MAX_LEVELS
         for lev in self.levels:
             assert 1 <= len(lev) <= abi.MAX_TASKS

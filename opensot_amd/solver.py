@@ -39,15 +39,21 @@ def stored_rows(plan, C_dense):
 class BatchedStack:
     """B independent instances of one static stack (same topology, different numbers)."""
 
-    def __init__(self, plan: StackPlan, max_batch: int, device: int = 0, want_levels: bool = True):
+    def __init__(self, plan: StackPlan, max_batch: int, device: int = 0, want_levels: bool = True, route: str = "auto"):
+        """route: "wavefront" (osot_solver_create, n <= 64: one wavefront per instance), "wide" (osot_solver_create_wide, n <= 128:
+        one 256-thread workgroup per instance; nHQP / eHQP, the fused control cycle, hot start and phase profiling are refused there),
+        "auto" (default): the wavefront route up to 64 variables, the wide route beyond."""
+        if route not in ("auto", "wavefront", "wide"):
+            raise ValueError(f"unknown route {route!r}")
         self.plan = plan
         self.max_batch = int(max_batch)
         self.device = torch.device("cuda", device)
         self._lib = abi.lib()   # raises NativeLibraryMissing when the HIP extension is not built
         self._cplan = plan.to_c()
+        self.route = route if route != "auto" else ("wide" if plan.n > abi.MAX_VARS else "wavefront")
         h = C.c_void_p()
-        abi.check(self._lib.osot_solver_create(C.byref(self._cplan), self.max_batch, device, C.byref(h)),
-                  "osot_solver_create")
+        create = "osot_solver_create_wide" if self.route == "wide" else "osot_solver_create"
+        abi.check(getattr(self._lib, create)(C.byref(self._cplan), self.max_batch, device, C.byref(h)), create)
         self._h = h
         n, L, B = plan.n, plan.L, self.max_batch
         f64 = dict(dtype=torch.float64, device=self.device)

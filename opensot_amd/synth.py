@@ -485,3 +485,48 @@ def wide_id_levels(rng, nv=56, ncon=5, tau_max=60.0):
         t = A0 @ xs[0]
         return H, g, np.vstack([Cm, A0]), np.concatenate([lo, t]), np.concatenate([up, t]), l, u
     return n, level
+
+
+def make_wide_robot_stack(B, n=96, levels=3, seed=0, eps_factor=1e6, n_ineq=16, n_local=8):
+    """a robot-like velocity stack WIDER than a wavefront (n = 65 .. 128: a 45-DoF humanoid with a floating base and hands): CoM and
+    the feet first, the hands and the head next, an implicit Postural block last (levels = 3; levels = 2 folds the first two), joint
+    and velocity limits, generic inequality rows on every level and task-local rows of the middle level (`task << constraint`).
+    Columns: the 6 floating-base coordinates, then five limbs of (n - 6) / 5 joints each.  Returns (plan, leaf) as
+    make_velocity_stack; the workgroup route (BatchedStack(route="wide")) and tools/bench_wide_plan.py run it."""
+    assert 7 <= n <= abi.MAX_QP_VARS and levels in (2, 3)
+    rng = np.random.default_rng(seed)
+    limb = (n - 6) // 5
+    limbs = {nm: list(range(6 + i * limb, 6 + (i + 1) * limb)) for i, nm in enumerate(("l_leg", "r_leg", "l_arm", "r_arm", "head"))}
+    limbs["head"] = list(range(6 + 4 * limb, n))      # (the remainder of the columns)
+
+    def cart(name, cols, weight=1.0, lam=0.1):
+        return Task(abi.TASK_CARTESIAN, 6, weight=weight, lam=lam, name=name), _limb_jacobian(rng, B, 6, n, _BASE + cols), _cartesian_leaf(rng, B)
+
+    def com(lam=0.1):
+        p = rng.uniform(-0.2, 0.2, size=(B, 3))
+        return (Task(abi.TASK_COM, 3, lam=lam, name="com"), rng.normal(0.0, 0.3, size=(B, 3, n)) / np.sqrt(n / 32.0),
+                (p, p + rng.uniform(-0.05, 0.05, size=(B, 3)), None))
+
+    bounds, bleaf = _box_leaf(rng, B, n, jl=True, vl=True)
+    first = [com(), cart("l_sole", limbs["l_leg"]), cart("r_sole", limbs["r_leg"])]
+    second = [cart("l_wrist", limbs["l_arm"], weight=0.1), cart("r_wrist", limbs["r_arm"]), cart("gaze", limbs["head"], weight=0.5)]
+    q = bleaf[0][0]
+    post = (Task(abi.TASK_POSTURAL, n, lam=0.01, name="postural"), None, (q, q + rng.normal(0.0, 0.1, size=(B, n)), None))
+    blocks = [first, second, [post]] if levels == 3 else [first + second, [post]]
+    plan_levels, A, tleaf = [], [], []
+    for lev in blocks:
+        plan_levels.append([t for (t, _, _) in lev])
+        Js = [J for (_, J, _) in lev if J is not None]
+        A.append(np.ascontiguousarray(np.concatenate(Js, axis=1)) if Js else None)
+        tleaf.append([lf for (_, _, lf) in lev])
+    rowblocks, rleaf = [], []
+    if n_ineq:
+        Ci = rng.normal(0.0, 0.3, size=(B, n_ineq, n)) / np.sqrt(n / 32.0)
+        rowblocks.append(Rows(abi.ROWS_GENERIC, n_ineq, name="inequalities"))
+        rleaf.append((Ci, -rng.uniform(0.01, 0.1, size=(B, n_ineq)), rng.uniform(0.01, 0.1, size=(B, n_ineq))))
+    if n_local:
+        Cl = rng.normal(0.0, 0.3, size=(B, n_local, n)) / np.sqrt(n / 32.0)
+        rowblocks.append(Rows(abi.ROWS_GENERIC, n_local, name="task_local", level=len(blocks) - 2))
+        rleaf.append((Cl, -rng.uniform(0.002, 0.02, size=(B, n_local)), rng.uniform(0.002, 0.02, size=(B, n_local))))
+    plan = StackPlan(n=n, levels=plan_levels, bounds=bounds, rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    return plan, {"B": B, "A": A, "task": tleaf, "bound": bleaf, "rows": rleaf}
