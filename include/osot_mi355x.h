@@ -161,17 +161,28 @@ typedef enum {
      * task_orientation_gain are the task's gains. */
     OSOT_ROWS_TASK_CARTESIAN = 7,     /* velocity::Cartesian as a constraint: 6 rows; leaf as for OSOT_TASK_CARTESIAN */
     OSOT_ROWS_TASK_COM = 8,           /* velocity::CoM as a constraint: 3 rows; leaf as for OSOT_TASK_COM */
-    OSOT_ROWS_UNIT_GENERIC = 9        /* unit rows e_(first_col+i) (NOT stored), lo / up supplied: a box on a range of
+    OSOT_ROWS_UNIT_GENERIC = 9,       /* unit rows e_(first_col+i) (NOT stored), lo / up supplied: a box on a range of
                                          variables as rows.  With only_level = k + 1 this is a TASK-LOCAL BOUND
                                          (`task << joint_limits`: iHQP merges a level's own bounds into that level's
-                                         box only, iHQP.cpp:190, 336-340) */
+                                         box only, iHQP.cpp:190, 336-340).  force::WrenchLimits is such a block on
+                                         a contact's 6 wrench columns (releaseContact: lo = up = 0) */
+    /* surface contacts: `contacts` consecutive 6-D wrenches [f_x f_y f_z tau_x tau_y tau_z], the wrench of contact ct in
+     * columns first_col + 6 ct .. + 5.  Stored rows (written into C by every update), lo = -1e20, up = 0.  Leaf p0 =
+     * wRl [B][contacts][9] row-major (the contact link's rotation, as for OSOT_ROWS_FRICTION_CONE); Ad = blockdiag(wRl', wRl')
+     * (_Ti.linear() of the contact pose T).  p1 = [B][contacts][4] (x_l, x_u, y_l, y_u): the X_Lims / Y_Lims of the foot. */
+    OSOT_ROWS_WRENCH_FRICTION_CONE = 10, /* force::FrictionCone on a wrench (FrictionCone.cpp:35-56): 5 rows per contact,
+                                            pyramid(mu/sqrt2) * wRl' on the force columns, 0 on the torque columns */
+    OSOT_ROWS_COP = 11,               /* force::CoP (CoP.cpp:24-69): 4 rows per contact, Ai * Ad (the CoP inside the
+                                         rectangle [x_l, x_u] x [y_l, y_u]) */
+    OSOT_ROWS_NORMAL_TORQUE = 12      /* force::NormalTorque (NormalTorque.cpp:5-69): 8 rows per contact, A0 * Ad2 * Ad
+                                         with mu = the block's mu */
 } osot_rows_kind;
 
 typedef struct {
     int kind;  /* osot_rows_kind */
     int rows;  /* for COLLISION: max_pairs */
     double d_threshold, detection_threshold, bound_scaling;
-    int first_col;   /* unit-row / friction-cone blocks: column of the block's first variable */
+    int first_col;   /* unit-row / friction-cone / surface-contact blocks: column of the block's first variable */
     double dT, p;    /* acceleration limits: time step and horizon factor (dt = dT*p) */
     double mu;       /* friction coefficient */
     double task_lambda, task_orientation_gain;   /* OSOT_ROWS_TASK_*: gains of the underlying task */
@@ -652,10 +663,12 @@ int osot_control_rollout(osot_solver* s, osot_kin* k, const osot_kin_batch* kin_
  * producers straight into their row ranges of the stacked A_k / C (zero-copy, like the kinematics producer's Jacobians);
  * the model quantities themselves (inertia matrix B, non-linear term h, contact Jacobians) come from the caller's
  * dynamics library, as they come from XBot::ModelInterface in the reference. */
-#define OSOT_ID_MAX_FORCE_VARS 24
+#define OSOT_ID_MAX_FORCE_VARS 48   /* eight surface contacts */
 typedef struct {
     int B, nv, n_contacts, contact_dim;   /* contact_dim: 3 = point contact (force), 6 = surface contact (wrench)
-                                             (InverseDynamics.cpp:16-27); nv + n_contacts * contact_dim <= OSOT_MAX_VARS */
+                                             (InverseDynamics.cpp:16-27); nv + n_contacts * contact_dim <=
+                                             OSOT_MAX_QP_VARS (128: the wide route) and n_contacts * contact_dim <=
+                                             OSOT_ID_MAX_FORCE_VARS                                                      */
     const double* Bm;                     /* [B][nv][nv] inertia matrix (symmetric)                                      */
     const double* h;                      /* [B][nv] non-linear term                                                     */
     const double* Jc;                     /* [B][n_contacts][contact_dim][nv] first contact_dim rows of each contact's
@@ -675,7 +688,7 @@ int osot_id_rows(const osot_id_model* m, double* C_dyn, long long dyn_stride, do
  * then Gp = Mi Kp, Gd = Mi Kd written into the task's leaf array p0 behind its 2 rows errors (see
  * osot_task_desc.acc_gain_matrices: p0_gains points at instance 0's Gp, p0_stride = 2 rows + 2 rows^2 doubles), and
  * a_ref[B][rows] += Mi f for a virtual force f [B][rows] (NULL: none).  Kp, Kd: HOST pointers to rows x rows row-major
- * matrices (the task's settings).  rows <= 6. */
+ * matrices (the task's settings).  rows <= 6, nv <= OSOT_MAX_QP_VARS. */
 int osot_id_force_gains(int B, int nv, int rows, const double* J, const double* Bi, const double* Kp, const double* Kd,
                         const double* f_virtual, double* p0_gains, long long p0_stride, double* a_ref, void* hip_stream);
 /* InverseDynamics::computedTorque (InverseDynamics.cpp:57-96): tau[B][nv] = B qddot + h - sum_c Jc' F_c from the solved

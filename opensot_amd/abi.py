@@ -7,7 +7,7 @@ import os
 
 MAX_LEVELS, MAX_TASKS, MAX_BOUNDS, MAX_ROWBLOCKS, MAX_VARS = 8, 8, 4, 8, 64
 MAX_QP_VARS = 128      # the explicit-QP surface (osot_qp_solve_batch, osot_backend_*): OSOT_MAX_QP_VARS
-MAX_BAND_ROWS, ID_MAX_FORCE_VARS = 6, 24
+MAX_BAND_ROWS, ID_MAX_FORCE_VARS = 6, 48
 
 OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_NOT_SOLVED, ERR_COMM = range(6)
 STATUS_SOLVED, STATUS_INFEASIBLE, STATUS_MAX_ITER, STATUS_NOT_PD = range(4)
@@ -15,6 +15,8 @@ TASK_GENERIC, TASK_CARTESIAN, TASK_COM, TASK_POSTURAL, TASK_ACC_CARTESIAN, TASK_
 BOUND_GENERIC, BOUND_JOINT_LIMITS, BOUND_VELOCITY_LIMITS = range(3)
 (ROWS_GENERIC, ROWS_COLLISION, ROWS_DYN_FEASIBILITY, ROWS_TORQUE_LIMITS, ROWS_FRICTION_CONE,
  ROWS_ACC_JOINT_LIMITS, ROWS_ACC_VELOCITY_LIMITS, ROWS_TASK_CARTESIAN, ROWS_TASK_COM, ROWS_UNIT_GENERIC) = range(10)
+# surface contacts: 6-D wrenches, 5 / 4 / 8 stored rows per contact (force::FrictionCone, force::CoP, force::NormalTorque)
+ROWS_WRENCH_FRICTION_CONE, ROWS_COP, ROWS_NORMAL_TORQUE = 10, 11, 12
 # OpenSoT::HessianType (include/OpenSoT/Task.h:33-41)
 HST_UNDEFINED, HST_ZERO, HST_IDENTITY, HST_POSDEF, HST_POSDEF_NULLSPACE, HST_SEMIDEF, HST_UNKNOWN = range(7)
 

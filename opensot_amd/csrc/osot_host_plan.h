@@ -144,7 +144,7 @@ inline int plan_validate(const osot_plan_desc* p, const char** why, int wide = 0
         if (p->bound[j].kind < 0 || p->bound[j].kind > OSOT_BOUND_VELOCITY_LIMITS) { *why = "unknown bound kind"; return OSOT_ERR_UNSUPPORTED; }
     for (int j = 0; j < p->n_rowblocks; ++j) {
         const osot_rows_desc& rb = p->rowblock[j];
-        if (rb.kind < 0 || rb.kind > OSOT_ROWS_UNIT_GENERIC) { *why = "unknown row-block kind"; return OSOT_ERR_UNSUPPORTED; }
+        if (rb.kind < 0 || rb.kind > OSOT_ROWS_NORMAL_TORQUE) { *why = "unknown row-block kind"; return OSOT_ERR_UNSUPPORTED; }
         if (rb.kind == OSOT_ROWS_TASK_CARTESIAN && rb.rows != 6) { *why = "a Cartesian task as a constraint has 6 rows"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_TASK_COM && rb.rows != 3) { *why = "a CoM task as a constraint has 3 rows"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_TASK_CARTESIAN || rb.kind == OSOT_ROWS_TASK_COM)
@@ -156,6 +156,15 @@ inline int plan_validate(const osot_plan_desc* p, const char** why, int wide = 0
         if (rb.kind == OSOT_ROWS_DYN_FEASIBILITY && rb.rows != 6) { *why = "DynamicFeasibility has 6 rows"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_FRICTION_CONE && (rb.rows % 5 != 0 || rb.first_col < 0 || rb.first_col + 3 * (rb.rows / 5) > p->n)) {
             *why = "friction cone block: rows = 5*contacts and 3 force columns per contact inside x"; return OSOT_ERR_INVALID; }
+        if (rb.kind >= OSOT_ROWS_WRENCH_FRICTION_CONE && rb.kind <= OSOT_ROWS_NORMAL_TORQUE) {   // 6 wrench columns per contact
+            const int per = rb.kind == OSOT_ROWS_WRENCH_FRICTION_CONE ? 5 : (rb.kind == OSOT_ROWS_COP ? 4 : 8);
+            if (rb.rows % per != 0 || rb.first_col < 0 || rb.first_col + 6 * (rb.rows / per) > p->n) {
+                *why = rb.kind == OSOT_ROWS_WRENCH_FRICTION_CONE ? "wrench friction cone block: rows = 5*contacts and 6 wrench columns per contact inside x"
+                     : (rb.kind == OSOT_ROWS_COP ? "CoP block: rows = 4*contacts and 6 wrench columns per contact inside x"
+                                                 : "normal torque block: rows = 8*contacts and 6 wrench columns per contact inside x");
+                return OSOT_ERR_INVALID;
+            }
+        }
         if (rows_are_implicit(rb.kind) && (rb.first_col < 0 || rb.first_col + rb.rows > p->n)) {
             *why = "unit-row block exceeds the variables"; return OSOT_ERR_INVALID; }
         if (rows_are_implicit(rb.kind) && rb.kind != OSOT_ROWS_UNIT_GENERIC && !(rb.dT * rb.p > 0.0)) { *why = "acceleration limits need dT*p > 0"; return OSOT_ERR_INVALID; }
@@ -369,6 +378,8 @@ inline int make_update_args(const osot_plan_desc& pl, const DevUpdatePlan& PL, c
             { *why = "leaf input p1 of a row block is null"; return OSOT_ERR_INVALID; }
         if (kind == OSOT_ROWS_ACC_JOINT_LIMITS && !d.p2) { *why = "acceleration joint limits need qddot_max"; return OSOT_ERR_INVALID; }
         if (kind == OSOT_ROWS_GENERIC && !d.p2) { *why = "generic rows need C, lo, up"; return OSOT_ERR_INVALID; }
+        if ((kind == OSOT_ROWS_COP || kind == OSOT_ROWS_NORMAL_TORQUE) && !d.p1)
+            { *why = "CoP / normal torque rows need the contact's x / y limits (p1)"; return OSOT_ERR_INVALID; }
     }
     if (PL.nc > 0 && (!out->lo || !out->up)) { *why = "out.lo/up is null"; return OSOT_ERR_INVALID; }
     if (PL.nc_stored > 0 && !out->C) { *why = "out.C is null"; return OSOT_ERR_INVALID; }

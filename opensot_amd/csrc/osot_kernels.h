@@ -1012,6 +1012,46 @@ __device__ inline void cartesian_b(const double* Ta, const double* Td, const dou
     }
 }
 
+// Entry (rr, col) of a surface contact's row block over its wrench [f_x f_y f_z tau_x tau_y tau_z]: a * Ad with
+// Ad = blockdiag(R', R') (_Ti.linear() of the contact pose), R = wRl row-major, so (a Ad)[col] = sum_k a[k] R[col][k] on the
+// force columns and sum_k a[3 + k] R[col - 3][k] on the torque columns.  a = row rr of
+//   kind 10, force::FrictionCone on a wrench (FrictionCone.cpp:35-56): the mu/sqrt(2) pyramid on f, 0 on tau
+//   kind 11, force::CoP (CoP.cpp:24-69): Ai, lim = (x_l, x_u, y_l, y_u)
+//   kind 12, force::NormalTorque (NormalTorque.cpp:5-69): A0 Ad2 (_updateA, the constructor's Ad2 and X, Y, K)
+__device__ inline double wrench_row_entry(int kind, int rr, int col, const double* R, const double* lim, double mu) {
+    double a[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (kind == 10) {
+        const double m = mu / sqrt(2.0);
+        a[0] = (rr == 0) ? 1.0 : (rr == 1 ? -1.0 : 0.0);
+        a[1] = (rr == 2) ? 1.0 : (rr == 3 ? -1.0 : 0.0);
+        a[2] = (rr == 4) ? -1.0 : -m;
+    } else if (kind == 11) {
+        const double xl = lim[0], xu = lim[1], yl = lim[2], yu = lim[3];
+        a[2] = rr == 0 ? xl : (rr == 1 ? -xu : (rr == 2 ? yl : -yu));
+        a[3] = rr == 2 ? -1.0 : (rr == 3 ? 1.0 : 0.0);
+        a[4] = rr == 0 ? 1.0 : (rr == 1 ? -1.0 : 0.0);
+    } else {
+        const double xl = lim[0], xu = lim[1], yl = lim[2], yu = lim[3];
+        const double X = (fabs(xl) + fabs(xu)) / 2., Y = (fabs(yl) + fabs(yu)) / 2.;
+        const double px = (xu + xl) / 2., py = (yu + yl) / 2.;
+        const double K = -mu * (X + Y);
+        // A0 row rr: (sy Y, sx X, K, sa mu, sb mu, sz), the signs of NormalTorque::_updateA
+        const double sy = (rr == 0 || rr == 1 || rr == 6 || rr == 7) ? -1.0 : 1.0;
+        const double sx = (rr == 0 || rr == 2 || rr == 5 || rr == 7) ? -1.0 : 1.0;
+        const double sa = (rr == 0 || rr == 1 || rr == 4 || rr == 5) ? -1.0 : 1.0;
+        const double sb = (rr == 0 || rr == 2 || rr == 4 || rr == 6) ? -1.0 : 1.0;
+        const double sz = rr < 4 ? 1.0 : -1.0;
+        const double a0 = sy * Y, a1 = sx * X, a3 = sa * mu, a4 = sb * mu;
+        // times Ad2 = I + (3,2) py + (4,2) -px + (5,0) -py + (5,1) px
+        a[0] = a0 - sz * py;
+        a[1] = a1 + sz * px;
+        a[2] = K + a3 * py - a4 * px;
+        a[3] = a3; a[4] = a4; a[5] = sz;
+    }
+    const int o = col < 3 ? 0 : 3, c = col < 3 ? col : col - 3;
+    return a[o] * R[c * 3 + 0] + a[o + 1] * R[c * 3 + 1] + a[o + 2] * R[c * 3 + 2];
+}
+
 // AutoStack::update() of one instance by one wavefront.  `args_global` = the kernel's DevUpdate as MEMORY (the kernarg
 // segment), `lds` = kUpdateLdsBytes of LDS.  First the per-call pointers and the static plan are staged into LDS by ONE
 // batch of 16-byte vector loads (6 per lane): after that every lane looks up its row's task, gains and pointers with
@@ -1269,6 +1309,18 @@ __device__ __forceinline__ void update_body(const DevUpdate* args_global, const 
                 const double ci1 = (rr == 2) ? 1.0 : (rr == 3 ? -1.0 : 0.0);
                 const double ci2 = (rr == 4) ? -1.0 : -mu;
                 Cb[(ct * 5 + rr) * n + rb.first_col + ct * 3 + col] = ci0 * R[col * 3 + 0] + ci1 * R[col * 3 + 1] + ci2 * R[col * 3 + 2];
+            }
+            for (int r = t; r < rb.rows; r += 64) { lob[r] = -1.0e20; upb[r] = 0.0; }
+        } else if (rb.kind >= 10 && rb.kind <= 12) {   // surface contacts: 6-D wrench per contact, see wrench_row_entry
+            const int per = rb.kind == 10 ? 5 : (rb.kind == 11 ? 4 : 8);
+            const int nct = rb.rows / per;
+            for (int e = t; e < rb.rows * n; e += 64) Cb[e] = 0.0;
+            __syncthreads();
+            for (int e = t; e < nct * per * 6; e += 64) {
+                const int ct = e / (per * 6), rr = (e / 6) % per, col = e % 6;
+                const double* R = rp.p0 + (inst * nct + ct) * 9;
+                const double* lim = rb.kind == 10 ? nullptr : rp.p1 + (inst * nct + ct) * 4;
+                Cb[(ct * per + rr) * n + rb.first_col + ct * 6 + col] = wrench_row_entry(rb.kind, rr, col, R, lim, rb.mu);
             }
             for (int r = t; r < rb.rows; r += 64) { lob[r] = -1.0e20; upb[r] = 0.0; }
         } else if (rb.kind == 5) {   // acceleration::JointLimits (constraints/acceleration/JointLimits.cpp:58-176)

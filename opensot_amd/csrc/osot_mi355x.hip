@@ -1307,7 +1307,7 @@ int id_model_check(const osot_id_model* m, int* n_out) {
     if (m->B < 0 || m->nv < 1 || m->n_contacts < 0) return fail(OSOT_ERR_INVALID, "bad sizes");
     if (m->contact_dim != 3 && m->contact_dim != 6) return fail(OSOT_ERR_INVALID, "Unsupported  contact model");   // InverseDynamics.cpp:27
     const int nf = m->n_contacts * m->contact_dim;
-    if (nf > OSOT_ID_MAX_FORCE_VARS || m->nv + nf > OSOT_MAX_VARS) return fail(OSOT_ERR_UNSUPPORTED, "nv + force variables exceed 64 (or forces exceed 24)");
+    if (nf > OSOT_ID_MAX_FORCE_VARS || m->nv + nf > OSOT_MAX_QP_VARS) return fail(OSOT_ERR_UNSUPPORTED, "nv + force variables exceed 128 (or forces exceed 48)");
     if (!m->Bm || (nf > 0 && !m->Jc)) return fail(OSOT_ERR_INVALID, "null B / Jc");
     *n_out = m->nv + nf;
     return OSOT_OK;
@@ -1343,7 +1343,7 @@ int osot_id_rows(const osot_id_model* m, double* C_dyn, long long dyn_stride, do
 
 int osot_id_force_gains(int B, int nv, int rows, const double* J, const double* Bi, const double* Kp, const double* Kd,
                         const double* f_virtual, double* p0_gains, long long p0_stride, double* a_ref, void* hip_stream) {
-    if (B < 0 || nv < 1 || nv > 64 || rows < 1 || rows > 6) return fail(OSOT_ERR_INVALID, "force gains: sizes out of range (nv <= 64, rows <= 6)");
+    if (B < 0 || nv < 1 || nv > OSOT_MAX_QP_VARS || rows < 1 || rows > 6) return fail(OSOT_ERR_INVALID, "force gains: sizes out of range (nv <= 128, rows <= 6)");
     if (B == 0) return OSOT_OK;
     if (!J || !Bi || !Kp || !Kd || !p0_gains) return fail(OSOT_ERR_INVALID, "force gains: null argument");
     if (f_virtual && !a_ref) return fail(OSOT_ERR_INVALID, "force gains: a virtual force needs a_ref to add Mi f to");
@@ -1351,7 +1351,8 @@ int osot_id_force_gains(int B, int nv, int rows, const double* J, const double* 
     std::memset(&F, 0, sizeof(F));
     F.B = B; F.nv = nv; F.rows = rows; F.J = J; F.Bi = Bi; F.f = f_virtual; F.G = p0_gains; F.G_stride = p0_stride; F.a_ref = a_ref;
     for (int i = 0; i < rows * rows; ++i) { F.Kp[i] = Kp[i]; F.Kd[i] = Kd[i]; }
-    hipLaunchKernelGGL(osot_force_gains_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)hip_stream, F);
+    if (nv <= 64) hipLaunchKernelGGL(osot_force_gains_kernel<64>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)hip_stream, F);
+    else hipLaunchKernelGGL(osot_force_gains_kernel<OSOT_MAX_QP_VARS>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)hip_stream, F);
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

@@ -270,11 +270,138 @@ def make_id_stack(B, seed=None, nv=38, n_contacts=4, eps_factor=1e6, torque_limi
     return plan, leaf
 
 
+def wrench_rows(kind, wRl, lims, mu):
+    """the rows of one surface contact over its wrench [f; tau] (numpy, [B][rows][6]): A * blockdiag(wRl', wRl') with A the
+    mu/sqrt(2) pyramid on f (force::FrictionCone, FrictionCone.cpp:35-56), Ai (force::CoP, CoP.cpp:24-69) or A0 * Ad2
+    (force::NormalTorque, NormalTorque.cpp:5-69).  wRl [B][3][3], lims [B][4] = (x_l, x_u, y_l, y_u)."""
+    B = wRl.shape[0]
+    if kind == abi.ROWS_WRENCH_FRICTION_CONE:
+        m = mu / np.sqrt(2.0)
+        A = np.zeros((B, 5, 6))
+        A[:, :, :3] = [[1, 0, -m], [-1, 0, -m], [0, 1, -m], [0, -1, -m], [0, 0, -1]]
+    else:
+        xl, xu, yl, yu = (lims[:, i] for i in range(4))
+        if kind == abi.ROWS_COP:
+            A = np.zeros((B, 4, 6))
+            A[:, 0, 2], A[:, 0, 4] = xl, 1.0
+            A[:, 1, 2], A[:, 1, 4] = -xu, -1.0
+            A[:, 2, 2], A[:, 2, 3] = yl, -1.0
+            A[:, 3, 2], A[:, 3, 3] = -yu, 1.0
+        else:
+            X = (np.abs(xl) + np.abs(xu)) / 2.0
+            Y = (np.abs(yl) + np.abs(yu)) / 2.0
+            K = -mu * (X + Y)
+            sgn = np.array([[-1, -1, -1, -1, 1], [-1, 1, -1, 1, 1], [1, -1, 1, -1, 1], [1, 1, 1, 1, 1],
+                            [1, 1, -1, -1, -1], [1, -1, -1, 1, -1], [-1, 1, 1, -1, -1], [-1, -1, 1, 1, -1]], dtype=float)
+            A = np.zeros((B, 8, 6))
+            A[:, :, 0] = sgn[None, :, 0] * Y[:, None]
+            A[:, :, 1] = sgn[None, :, 1] * X[:, None]
+            A[:, :, 2] = K[:, None]
+            A[:, :, 3] = sgn[None, :, 2] * mu
+            A[:, :, 4] = sgn[None, :, 3] * mu
+            A[:, :, 5] = sgn[None, :, 4]
+            Ad2 = np.broadcast_to(np.eye(6), (B, 6, 6)).copy()
+            px, py = (xu + xl) / 2.0, (yu + yl) / 2.0
+            Ad2[:, 3, 2], Ad2[:, 4, 2], Ad2[:, 5, 0], Ad2[:, 5, 1] = py, -px, -py, px
+            A = A @ Ad2
+    Ad = np.zeros((B, 6, 6))
+    Rt = np.transpose(wRl, (0, 2, 1))
+    Ad[:, :3, :3] = Rt
+    Ad[:, 3:, 3:] = Rt
+    return A @ Ad
+
+
+def make_surface_id_stack(B, seed=None, nv=44, n_contacts=4, eps_factor=1e6):
+    """floating-base inverse dynamics with SURFACE contacts: x = [qddot (nv); 6-D wrench [f; tau] per contact] (contact_dim = 6,
+    src/utils/InverseDynamics.cpp:16-27): the feet and hands of a humanoid that stands and holds.  n = nv + 6 contacts; up to 64
+    the wavefront route, 65 .. 128 the wide route (BatchedStack(route="auto")).
+
+    levels : 0 = acceleration::CoM (3) + two acceleration::Cartesian (6 each)      [J 0] written by the producer
+             1 = acceleration::Postural on qddot ([I_nv 0], implicit)
+    rows   : DynamicFeasibility (6 eq) [B_u, -J_f'], force::FrictionCone on the wrenches (5 per contact), force::CoP (4 per
+             contact), force::NormalTorque (8 per contact), TorqueLimits (nv) [B, -Jc'], acceleration::JointLimits (nv unit
+             rows), force::WrenchLimits as unit rows on the wrench columns (6 per contact) -- seven blocks
+    Feasible by construction: the nominal (qddot = 0, W0) is dynamically consistent on the floating base and W0 lies strictly
+    inside every friction, CoP and normal-torque row (asserted); torque limits are tight enough that some bind."""
+    rng = np.random.default_rng(7000 if seed is None else seed)
+    nf = 6 * n_contacts
+    n = nv + nf
+    assert n <= abi.MAX_QP_VARS and nf <= abi.ID_MAX_FORCE_VARS and nv >= 16
+    mu = 0.8
+    # dynamics: B = L L' + I; each contact's 6 x nv Jacobian acts on the floating base and on a limb of 6 joints
+    Lm = rng.normal(0.0, 0.3, size=(B, nv, nv))
+    Bm = Lm @ np.transpose(Lm, (0, 2, 1)) + np.eye(nv)
+    Jc = np.zeros((B, n_contacts, 6, nv))
+    Jc[:, :, :, :6] = rng.normal(0.0, 0.5, size=(B, n_contacts, 6, 6))
+    for ct in range(n_contacts):
+        cols = 6 + (6 * ct + np.arange(6)) % (nv - 6)
+        Jc[:, ct][:, :, cols] = rng.normal(0.0, 0.3, size=(B, 6, 6))
+    # contact frames, foot rectangles and a nominal wrench inside every row: the CoP near the rectangle's middle, small
+    # tangential forces and normal torque
+    wRl = _rot_exp(rng.normal(0.0, 0.15, size=(B, n_contacts, 3)))
+    lims = np.stack([rng.uniform(-0.12, -0.08, size=(B, n_contacts)), rng.uniform(0.10, 0.15, size=(B, n_contacts)),
+                     rng.uniform(-0.07, -0.05, size=(B, n_contacts)), rng.uniform(0.05, 0.07, size=(B, n_contacts))], axis=2)
+    fz = rng.uniform(40.0, 80.0, size=(B, n_contacts))
+    f_loc = np.stack([rng.uniform(-3, 3, size=(B, n_contacts)), rng.uniform(-3, 3, size=(B, n_contacts)), fz], axis=2)
+    cx = (lims[..., 0] + lims[..., 1]) / 2 + rng.uniform(-0.01, 0.01, size=(B, n_contacts))
+    cy = (lims[..., 2] + lims[..., 3]) / 2 + rng.uniform(-0.01, 0.01, size=(B, n_contacts))
+    t_loc = np.stack([cy * fz, -cx * fz, rng.uniform(-0.3, 0.3, size=(B, n_contacts))], axis=2)
+    W0 = np.concatenate([np.einsum("bcij,bcj->bci", wRl, f_loc), np.einsum("bcij,bcj->bci", wRl, t_loc)], axis=2)
+    for kind in (abi.ROWS_WRENCH_FRICTION_CONE, abi.ROWS_COP, abi.ROWS_NORMAL_TORQUE):
+        for ct in range(n_contacts):
+            v = np.einsum("brj,bj->br", wrench_rows(kind, wRl[:, ct], lims[:, ct], mu), W0[:, ct])
+            assert v.max() < -1e-3, (kind, ct, v.max())
+    h = np.einsum("bcij,bci->bj", Jc, W0) + np.concatenate([np.zeros((B, 6)), rng.normal(0.0, 5.0, size=(B, nv - 6))], axis=1)
+    tau_max = np.full((B, nv), 30.0)
+    tau_max[:, :6] = 1.0e3
+    # tasks: CoM and the two hands on qddot
+    Jcom = rng.normal(0.0, 0.3, size=(B, 3, nv))
+    Jh = [_limb_jacobian(rng, B, 6, nv, list(range(0, 6)) + list(range(nv - 8 + 4 * k, nv - 4 + 4 * k))) for k in range(2)]
+    A0 = np.zeros((B, 15, n))
+    A0[:, 0:3, :nv] = Jcom
+    A0[:, 3:9, :nv] = Jh[0]
+    A0[:, 9:15, :nv] = Jh[1]
+
+    def acc_leaf(rows):
+        pe = rng.normal(0.0, 0.02, size=(B, rows)); ve = rng.normal(0.0, 0.05, size=(B, rows))
+        return np.concatenate([pe, ve], axis=1), rng.normal(0.0, 0.1, size=(B, rows)), None
+    q = rng.uniform(-1.0, 1.0, size=(B, nv)); qd = rng.normal(0.0, 0.2, size=(B, nv))
+    half = rng.uniform(1.5, 2.5, size=(B, nv))
+    levels = [[Task(abi.TASK_ACC_COM, 3, lam=10.0, lam2=5.0, name="com"),
+               Task(abi.TASK_ACC_CARTESIAN, 6, lam=10.0, lam2=5.0, name="l_hand"),
+               Task(abi.TASK_ACC_CARTESIAN, 6, lam=10.0, lam2=5.0, name="r_hand")],
+              [Task(abi.TASK_ACC_POSTURAL, nv, lam=10.0, lam2=5.0, name="postural")]]
+    tleaf = [[acc_leaf(3), acc_leaf(6), acc_leaf(6)],
+             [(np.concatenate([rng.normal(0.0, 0.1, size=(B, nv)), -qd], axis=1), None, None)]]
+    Cdyn = np.zeros((B, 6, n)); Ctau = np.zeros((B, nv, n))
+    Cdyn[:, :, :nv] = Bm[:, :6, :]
+    Ctau[:, :, :nv] = Bm
+    for ct in range(n_contacts):
+        Cdyn[:, :, nv + 6 * ct: nv + 6 * ct + 6] = -np.transpose(Jc[:, ct][:, :, :6], (0, 2, 1))
+        Ctau[:, :, nv + 6 * ct: nv + 6 * ct + 6] = -np.transpose(Jc[:, ct], (0, 2, 1))
+    R9, L4 = np.ascontiguousarray(wRl.reshape(B, n_contacts, 9)), np.ascontiguousarray(lims)
+    wl = np.tile(np.array([-1.0e3, -1.0e3, -1.0e3, -200.0, -200.0, -200.0]), (B, n_contacts))   # WrenchLimits
+    rowblocks = [Rows(abi.ROWS_DYN_FEASIBILITY, 6, name="dynamic_feasibility"),
+                 Rows(abi.ROWS_WRENCH_FRICTION_CONE, 5 * n_contacts, first_col=nv, mu=mu, name="friction_cones"),
+                 Rows(abi.ROWS_COP, 4 * n_contacts, first_col=nv, name="cop"),
+                 Rows(abi.ROWS_NORMAL_TORQUE, 8 * n_contacts, first_col=nv, mu=mu, name="normal_torque"),
+                 Rows(abi.ROWS_TORQUE_LIMITS, nv, name="torque_limits"),
+                 Rows(abi.ROWS_ACC_JOINT_LIMITS, nv, first_col=0, dT=0.001, p=20.0, name="joint_limits"),
+                 Rows(abi.ROWS_UNIT_GENERIC, nf, first_col=nv, name="wrench_limits")]
+    rleaf = [(h[:, :6].copy(), None, None), (R9, None, None), (R9, L4, None), (R9, L4, None), (h, tau_max, None),
+             (np.concatenate([q, qd], axis=1), np.concatenate([-half, half], axis=1), np.full((B, nv), 500.0)), (wl, -wl, None)]
+    Cleaf = [Cdyn, None, None, None, Ctau, None, None]
+    plan = StackPlan(n=n, levels=levels, bounds=[], rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [A0, None], "task": tleaf, "bound": [], "rows": rleaf, "C": Cleaf,
+            "model": {"B": Bm, "h": h, "Jc": Jc, "nv": nv}, "nominal": np.concatenate([np.zeros((B, nv)), W0.reshape(B, nf)], axis=1)}
+    return plan, leaf
+
+
 def computed_torque(leaf, x):
     """InverseDynamics::computedTorque (src/utils/InverseDynamics.cpp:57-96): tau = B qddot + h - sum_c Jc' F_c;
-    the six floating-base rows must vanish."""
+    the six floating-base rows must vanish.  The contact dimension (3: point contacts, 6: surface contacts) is Jc's."""
     md = leaf["model"]; nv = md["nv"]
-    qdd = x[:, :nv]; F = x[:, nv:].reshape(x.shape[0], -1, 3)
+    qdd = x[:, :nv]; F = x[:, nv:].reshape(x.shape[0], -1, md["Jc"].shape[2])
     return np.einsum("bij,bj->bi", md["B"], qdd) + md["h"] - np.einsum("bcij,bci->bj", md["Jc"], F)
 
 

@@ -1,0 +1,174 @@
+"""Surface-contact constraints restated in numpy (test infrastructure): force::FrictionCone on a 6-D wrench, force::CoP and
+force::NormalTorque of the reference (src/constraints/force/FrictionCone.cpp:35-56, CoP.cpp:24-69, NormalTorque.cpp:5-69), one
+contact and one instance at a time, in the order the reference builds its matrices.  The oracle knows nothing of these row kinds,
+so every comparison with it goes through the GENERIC TWIN of a plan: the same stack with each surface block replaced by an
+OSOT_ROWS_GENERIC block carrying the rows written out here."""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from opensot_amd import abi
+from opensot_amd.plan import Rows, StackPlan
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SURFACE_KINDS = {abi.ROWS_WRENCH_FRICTION_CONE: 5, abi.ROWS_COP: 4, abi.ROWS_NORMAL_TORQUE: 8}
+
+
+def _Ad(wRl):
+    """_Ad.block<3,3>(0,0) = _Ad.block<3,3>(3,3) = _Ti.linear() with _T the contact pose: the transpose of wRl"""
+    Ad = np.zeros((6, 6))
+    Ad[:3, :3] = wRl.T
+    Ad[3:, 3:] = wRl.T
+    return Ad
+
+
+def friction_cone(wRl, mu):
+    """FrictionCone::computeAineq with a 6-D wrench: _A.block<5,3>(0,0) = Ci * wRl', zero on the torque columns"""
+    m = mu / np.sqrt(2.0)
+    Ci = np.array([[1., 0., -m], [-1., 0., -m], [0., 1., -m], [0., -1., -m], [0., 0., -1.]])
+    A = np.zeros((5, 6))
+    A[:, :3] = Ci @ wRl.T
+    return A
+
+
+def cop(wRl, lim):
+    """CoP::CoP / CoP::update: _Ai * _Ad"""
+    xl, xu, yl, yu = lim
+    Ai = np.zeros((4, 6))
+    Ai[0, 2], Ai[0, 4] = xl, 1.
+    Ai[1, 2], Ai[1, 4] = -xu, -1.
+    Ai[2, 2], Ai[2, 3] = yl, -1.
+    Ai[3, 2], Ai[3, 3] = -yu, 1.
+    return Ai @ _Ad(wRl)
+
+
+def normal_torque(wRl, lim, mu):
+    """NormalTorque::NormalTorque / _updateA / update: (_A * _Ad2) * _Ad"""
+    xl, xu, yl, yu = lim
+    Ad2 = np.eye(6)
+    px, py = (xu + xl) / 2., (yu + yl) / 2.
+    Ad2[3, 2] = py
+    Ad2[4, 2] = -px
+    Ad2[5, 0], Ad2[5, 1] = -py, px
+    X = (abs(xl) + abs(xu)) / 2.
+    Y = (abs(yl) + abs(yu)) / 2.
+    K = -mu * (X + Y)
+    A = np.array([[-Y, -X, K, -mu, -mu, 1], [-Y, X, K, -mu, mu, 1], [Y, -X, K, mu, -mu, 1], [Y, X, K, mu, mu, 1],
+                  [Y, X, K, -mu, -mu, -1], [Y, -X, K, -mu, mu, -1], [-Y, X, K, mu, -mu, -1], [-Y, -X, K, mu, mu, -1]], dtype=float)
+    return (A @ Ad2) @ _Ad(wRl)
+
+
+def surface_block(rb, p0, p1, n):
+    """(C [B][rows][n], lo [B][rows], up [B][rows]) of a surface row block rb (plan.Rows) from its leaf inputs"""
+    per = SURFACE_KINDS[rb.kind]
+    B, nct = p0.shape[0], rb.rows // per
+    Cb = np.zeros((B, rb.rows, n))
+    for i in range(B):
+        for ct in range(nct):
+            R = np.asarray(p0[i, ct], dtype=float).reshape(3, 3)
+            if rb.kind == abi.ROWS_WRENCH_FRICTION_CONE:
+                A = friction_cone(R, rb.mu)
+            elif rb.kind == abi.ROWS_COP:
+                A = cop(R, p1[i, ct])
+            else:
+                A = normal_torque(R, p1[i, ct], rb.mu)
+            c0 = rb.first_col + 6 * ct
+            Cb[i, per * ct:per * (ct + 1), c0:c0 + 6] = A
+    return Cb, np.full((B, rb.rows), -1.0e20), np.zeros((B, rb.rows))
+
+
+def generic_twin(plan, leaf):
+    """the same stack with every surface block as OSOT_ROWS_GENERIC rows (C, lo, up) -> (plan, leaf)"""
+    blocks, rows, Cl = [], [], []
+    for j, rb in enumerate(plan.rowblocks):
+        if rb.kind in SURFACE_KINDS:
+            p0, p1, _ = leaf["rows"][j]
+            blocks.append(Rows(abi.ROWS_GENERIC, rb.rows, name=rb.name + "_generic", level=rb.level))
+            rows.append(surface_block(rb, p0, p1, plan.n))
+            Cl.append(None)
+        else:
+            blocks.append(rb)
+            rows.append(leaf["rows"][j])
+            Cl.append(leaf["C"][j])
+    twin = StackPlan(n=plan.n, levels=plan.levels, bounds=plan.bounds, rowblocks=blocks, eps_abs=plan.eps_abs, max_iter=plan.max_iter)
+    tleaf = dict(leaf)
+    tleaf["rows"], tleaf["C"] = rows, Cl
+    return twin, tleaf
+
+
+# ---- the host shim (tests/emu/surface_host.cpp) --------------------------------------------------------------------------------
+_lib = None
+
+
+def surface_lib():
+    global _lib
+    if _lib is None:
+        so = os.path.join(ROOT, "tests", "emu", "libosot_surface_host.so")
+        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_kernels.h", "osot_id.h", "osot_host_plan.h")] + \
+               [os.path.join(ROOT, "include", "osot_mi355x.h"), os.path.join(ROOT, "tests", "emu", "surface_host.cpp")]
+        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
+            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build_surface.sh")])
+        L = C.CDLL(so)
+        vp = C.c_void_p
+        L.surf_stack_update.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.LeafBatch), C.POINTER(abi.AssembledOut), C.c_int]
+        L.surf_id_rows.argtypes = [C.POINTER(abi.IdModel), vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, vp, vp, vp]
+        L.surf_computed_torque.argtypes = [C.POINTER(abi.IdModel), vp, vp, vp, C.c_double]
+        L.surf_force_gains.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, C.c_longlong, vp]
+        _lib = L
+    return _lib
+
+
+def host_update(fn, plan, leaf, *extra):
+    """AutoStack::update through an emulated update entry fn(plan, leaf, out, *extra) on host arrays (stacks without bounds,
+    dense weights or regularisation) -> (rc, {"b", "C" (stored rows), "lo", "up"})"""
+    B, n, L = leaf["B"], plan.n, plan.L
+    keep = []
+
+    def p(a):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        keep.append(a)
+        return a.ctypes.data
+    lb = abi.LeafBatch(); lb.B = B
+    for k, lev in enumerate(leaf["task"]):
+        for j, (p0, p1, p2) in enumerate(lev):
+            lb.task[k][j].p0, lb.task[k][j].p1, lb.task[k][j].p2 = p(p0), p(p1), p(p2)
+    for j, (p0, p1, p2) in enumerate(leaf["rows"]):
+        lb.rows[j].p0, lb.rows[j].p1, lb.rows[j].p2 = p(p0), p(p1), p(p2)
+    out = abi.AssembledOut()
+    res = {"b": [np.zeros((B, plan.m(k))) for k in range(L)], "w": [np.ones((B, plan.m(k))) for k in range(L)],
+           "C": np.full((B, plan.nc_stored, n), 7.0), "lo": np.zeros((B, plan.nc)), "up": np.zeros((B, plan.nc))}
+    for k in range(L):
+        out.b[k], out.w[k] = res["b"][k].ctypes.data, res["w"][k].ctypes.data
+    for j, Cj in enumerate(leaf.get("C", [])):
+        if Cj is not None:
+            o = plan.rows_stored_offset(j)
+            res["C"][:, o:o + Cj.shape[1]] = Cj
+    out.C, out.lo, out.up = res["C"].ctypes.data, res["lo"].ctypes.data, res["up"].ctypes.data
+    pd = plan.to_c()
+    rc = fn(C.byref(pd), C.byref(lb), C.byref(out), *extra)
+    return rc, res
+
+
+def id_model(leaf, keep, B=None):
+    md = leaf["model"]
+    Jc = np.ascontiguousarray(md["Jc"]); Bm = np.ascontiguousarray(md["B"]); h = np.ascontiguousarray(md["h"])
+    keep += [Jc, Bm, h]
+    m = abi.IdModel()
+    m.B, m.nv, m.n_contacts, m.contact_dim, m.floating_base = Bm.shape[0] if B is None else B, md["nv"], Jc.shape[1], Jc.shape[2], 1
+    m.Bm, m.h, m.Jc = Bm.ctypes.data, h.ctypes.data, Jc.ctypes.data
+    return m
+
+
+def torque(leaf, x):
+    """tau = B qddot + h - sum_c Jc' W_c written out per contact (InverseDynamics.cpp:57-96)"""
+    md = leaf["model"]
+    nv, Jc = md["nv"], md["Jc"]
+    tau = np.einsum("bij,bj->bi", md["B"], x[:, :nv]) + md["h"]
+    for ct in range(Jc.shape[1]):
+        d = Jc.shape[2]
+        tau -= np.einsum("bij,bi->bj", Jc[:, ct], x[:, nv + d * ct: nv + d * (ct + 1)])
+    return tau
