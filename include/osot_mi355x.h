@@ -662,7 +662,8 @@ int osot_control_rollout(osot_solver* s, osot_kin* k, const osot_kin_batch* kin_
  * (src/utils/InverseDynamics.cpp:12-28).  The matrices that are pure copies of model quantities are written by these
  * producers straight into their row ranges of the stacked A_k / C (zero-copy, like the kinematics producer's Jacobians);
  * the model quantities themselves (inertia matrix B, non-linear term h, contact Jacobians) come from the caller's
- * dynamics library, as they come from XBot::ModelInterface in the reference. */
+ * dynamics library, as they come from XBot::ModelInterface in the reference -- or from osot_dynamics / osot_kinematics below,
+ * which write them into these arrays on the device. */
 #define OSOT_ID_MAX_FORCE_VARS 48   /* eight surface contacts */
 typedef struct {
     int B, nv, n_contacts, contact_dim;   /* contact_dim: 3 = point contact (force), 6 = surface contact (wrench)
@@ -695,6 +696,46 @@ int osot_id_force_gains(int B, int nv, int rows, const double* J, const double* 
  * x[B][n]; ok[B] (may be NULL) = 0 where a floating-base row of tau exceeds fb_tol (the reference uses 10e-3 and
  * returns false). */
 int osot_computed_torque(const osot_id_model* m, const double* x, double* tau, int* ok, double fb_tol, void* hip_stream);
+
+/* ---- batched rigid-body dynamics producer ------------------------------------------------------------------------
+ * What the inverse-dynamics leaves ask XBot::ModelInterface for every cycle: computeInertiaMatrix (DynamicFeasibility.cpp:24,
+ * TorqueLimits.cpp:27, variables/Torque.cpp:32), computeNonlinearTerm (DynamicFeasibility.cpp:25, TorqueLimits.cpp:28,
+ * Torque.cpp:52), getJdotTimesV (acceleration/Cartesian.cpp:137, Contact.cpp:10) and getCOMJdotTimesV (acceleration/CoM.cpp:80),
+ * for the tree of an osot_kin_desc plus the rotational inertia of its links.  Like the kinematics producer it is an own
+ * implementation (xbot2_interface is not vendored); parity is pinned by a numpy restatement by another algorithm, by identities
+ * against osot_kinematics and by finite differences.  Conventions:
+ *   M qddot + h = tau + sum_c Jc' F_c: h holds the Coriolis, centrifugal AND gravity terms (computeNonlinearTerm); M and h are in
+ *   the tree's generalised coordinates, so with the usual floating-base chain their first six rows are the floating base's;
+ *   frame_Jdot_qdot = [classical acceleration of the frame origin; angular acceleration] at qddot = 0, world frame, such that
+ *   d/dt (J qdot) = J qddot + Jdot qdot with the world-frame J osot_kinematics writes; com_Jdot_qdot likewise for the CoM.
+ * M is written from one computed value per unordered pair (exactly symmetric). */
+typedef struct {
+    double inertia[OSOT_KIN_MAX_JOINTS][6];  /* Ixx Ixy Ixz Iyy Iyz Izz of the link joint j moves, about ITS CENTRE OF MASS
+                                                (osot_kin_desc.com[j]), axes of the joint frame; all zero = point mass       */
+    double gravity[3];                       /* world frame, e.g. (0, 0, -9.81)                                             */
+} osot_dyn_desc;
+typedef struct {
+    int B;
+    const double* q;                         /* [B][n]                                                                      */
+    const double* qdot;                      /* [B][n], NULL = zero (h is then the gravity term)                            */
+    double* M;                               /* first element of instance 0, or NULL                                        */
+    long long M_stride;                      /* doubles from one instance to the next (n * n when dense)                    */
+    double* h;                               /* [B][n] or NULL                                                              */
+    double* frame_Jdot_qdot[OSOT_KIN_MAX_FRAMES];          /* [linear; angular] of frame f in instance 0, or NULL           */
+    long long frame_Jdot_qdot_stride[OSOT_KIN_MAX_FRAMES]; /* doubles from one instance to the next (6 when dense): lets it
+                                                              land in a task's leaf array p1                                */
+    double* com_Jdot_qdot;                   /* 3 doubles per instance, or NULL                                             */
+    long long com_Jdot_qdot_stride;          /* (3 when dense)                                                              */
+} osot_dyn_batch;
+typedef struct osot_dyn osot_dyn;
+/* tree: what osot_kin_create takes (frames included; collision pairs are ignored).  Refused with OSOT_ERR_INVALID before any
+ * device is touched: joints out of tree order or out of range, axes that are not unit vectors, NaNs, negative masses, an
+ * inertia tensor that is not positive semi-definite or violates the triangle inequalities of its principal moments. */
+int osot_dyn_create(const osot_kin_desc* tree, const osot_dyn_desc* inertia, int device, osot_dyn** out);
+int osot_dyn_destroy(osot_dyn* d);
+/* Stream-ordered, no allocation, capturable.  Jdot qdot of a frame with frame_base != 0 or frame_body != 0 is refused
+ * (OSOT_ERR_UNSUPPORTED; the reference leaves the relative case open as well, acceleration/Cartesian.cpp:144). */
+int osot_dynamics(osot_dyn* d, const osot_dyn_batch* batch, void* hip_stream);
 
 /* ---- layout of the structs above as THIS library was compiled (for bindings that mirror them by hand: ctypes, cgo, JNI ...).
  * name = the typedef's name ("osot_plan_desc", "osot_qp_batch", ...).  *size = sizeof; the byte offset of every member, in

@@ -142,13 +142,24 @@ class KinBatch(C.Structure):
                 ("env_pose", C.c_void_p), ("env_pose_stride", C.c_longlong)]
 
 
+class DynDesc(C.Structure):
+    _fields_ = [("inertia", (C.c_double * 6) * KIN_MAX_JOINTS), ("gravity", C.c_double * 3)]
+
+
+class DynBatch(C.Structure):
+    _fields_ = [("B", C.c_int), ("q", C.c_void_p), ("qdot", C.c_void_p), ("M", C.c_void_p), ("M_stride", C.c_longlong),
+                ("h", C.c_void_p), ("frame_Jdot_qdot", C.c_void_p * KIN_MAX_FRAMES),
+                ("frame_Jdot_qdot_stride", C.c_longlong * KIN_MAX_FRAMES),
+                ("com_Jdot_qdot", C.c_void_p), ("com_Jdot_qdot_stride", C.c_longlong)]
+
+
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
     "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
-    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
+    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
     "osot_backend_create", "osot_backend_destroy", "osot_backend_init_problem",
     "osot_backend_update_task", "osot_backend_update_constraints", "osot_backend_update_bounds",
     "osot_backend_solve", "osot_backend_get_solution", "osot_backend_get_objective",
@@ -163,7 +174,8 @@ SYMBOLS = [
 STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound_desc": BoundDesc, "osot_rows_desc": RowsDesc,
            "osot_plan_desc": PlanDesc, "osot_qp_batch": QpBatch, "osot_leaf_ptrs": LeafPtrs, "osot_leaf_batch": LeafBatch,
            "osot_assembled_out": AssembledOut, "osot_backend_options": BackendOptions, "osot_nhqp_options": NhqpOptions,
-           "osot_admm_options": AdmmOptions, "osot_id_model": IdModel, "osot_kin_desc": KinDesc, "osot_kin_batch": KinBatch}
+           "osot_admm_options": AdmmOptions, "osot_id_model": IdModel, "osot_kin_desc": KinDesc, "osot_kin_batch": KinBatch,
+           "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -219,6 +231,9 @@ def lib():
     L.osot_kin_create.argtypes = [C.POINTER(KinDesc), C.c_int, C.POINTER(vp)]
     L.osot_kin_destroy.argtypes = [vp]
     L.osot_kinematics.argtypes = [vp, C.POINTER(KinBatch), vp]
+    L.osot_dyn_create.argtypes = [C.POINTER(KinDesc), C.POINTER(DynDesc), C.c_int, C.POINTER(vp)]
+    L.osot_dyn_destroy.argtypes = [vp]
+    L.osot_dynamics.argtypes = [vp, C.POINTER(DynBatch), vp]
     L.osot_control_cycle.argtypes = [vp, vp, C.POINTER(KinBatch), C.POINTER(LeafBatch), C.POINTER(AssembledOut), C.POINTER(QpBatch), vp, vp]
     L.osot_control_rollout.argtypes = [vp, vp, C.POINTER(KinBatch), C.POINTER(LeafBatch), C.POINTER(AssembledOut), C.POINTER(QpBatch), vp, C.c_int, vp, vp, vp]
     L.osot_solver_profile_phases.argtypes = [vp, C.POINTER(QpBatch), vp, vp]

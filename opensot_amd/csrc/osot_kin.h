@@ -53,6 +53,19 @@ inline void kin_build_tables(DevKin& h) {
     }
 }
 
+// osot_kin_create's checks of the frames (shared with osot_dyn_create, osot_dyn.h): the joint a frame is attached to, its
+// relative base link (Cartesian.cpp:40-51: a base link that is not the distal link)
+inline int kin_check_frames(const osot_kin_desc* d, const char** why) {
+    for (int f = 0; f < d->n_frames; ++f)
+        if (d->frame_joint[f] < 0 || d->frame_joint[f] >= d->n) { *why = "frame attached to a joint out of range"; return OSOT_ERR_INVALID; }
+    for (int f = 0; f < d->n_frames; ++f)
+        if (d->frame_base[f] < 0 || d->frame_base[f] > d->n_frames || d->frame_base[f] == f + 1) {
+            *why = "frame_base must be 0 (world) or 1 + the index of another frame";
+            return OSOT_ERR_INVALID;
+        }
+    return OSOT_OK;
+}
+
 __device__ __forceinline__ void mat3_mul(const double* A, const double* B, double* C) {
 #pragma unroll
     for (int i = 0; i < 3; ++i)

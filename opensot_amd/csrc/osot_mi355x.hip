@@ -17,6 +17,7 @@
 
 #include "osot_host_plan.h"
 #include "osot_kin.h"
+#include "osot_dyn.h"
 #include "osot_control.h"
 #include "osot_ehqp.h"
 #include "osot_id.h"
@@ -169,6 +170,9 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
         OSOT_F(pair_box) OSOT_F(pair_shape_R) OSOT_F(pair_shape_p) OSOT_F(n_env) OSOT_F(frame_base) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_kin_batch) OSOT_F(B) OSOT_F(q) OSOT_F(frame_pose) OSOT_F(frame_J) OSOT_F(frame_J_stride) OSOT_F(com)
         OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(pair_dist) OSOT_F(pair_J) OSOT_F(pair_J_stride) OSOT_F(env_pose) OSOT_F(env_pose_stride) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_dyn_desc) OSOT_F(inertia) OSOT_F(gravity) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_dyn_batch) OSOT_F(B) OSOT_F(q) OSOT_F(qdot) OSOT_F(M) OSOT_F(M_stride) OSOT_F(h) OSOT_F(frame_Jdot_qdot)
+        OSOT_F(frame_Jdot_qdot_stride) OSOT_F(com_Jdot_qdot) OSOT_F(com_Jdot_qdot_stride) OSOT_LAYOUT_END()
 #undef OSOT_LAYOUT_BEGIN
 #undef OSOT_F
 #undef OSOT_LAYOUT_END
@@ -1195,11 +1199,11 @@ int osot_kin_create(const osot_kin_desc* d, int device, osot_kin** out) {
         if (d->type[j] != OSOT_JOINT_REVOLUTE && d->type[j] != OSOT_JOINT_PRISMATIC) return fail(OSOT_ERR_INVALID, "unknown joint type");
     }
     kin_build_tables(h);
-    for (int f = 0; f < d->n_frames; ++f)
-        if (d->frame_joint[f] < 0 || d->frame_joint[f] >= d->n) return fail(OSOT_ERR_INVALID, "frame attached to a joint out of range");
-    for (int f = 0; f < d->n_frames; ++f)      // relative base link (Cartesian.cpp:40-51: a base link that is not the distal link)
-        if (d->frame_base[f] < 0 || d->frame_base[f] > d->n_frames || d->frame_base[f] == f + 1)
-            return fail(OSOT_ERR_INVALID, "frame_base must be 0 (world) or 1 + the index of another frame");
+    {
+        const char* why = "";
+        const int rc = kin_check_frames(d, &why);
+        if (rc != OSOT_OK) return fail(rc, why);
+    }
     if (d->n_pairs < 0 || d->n_pairs > OSOT_KIN_MAX_PAIRS) return fail(OSOT_ERR_INVALID, "collision pair count out of range");
     if (d->n_env < 0 || d->n_env > OSOT_KIN_MAX_ENV) return fail(OSOT_ERR_INVALID, "environment shape count out of range");
     for (int p = 0; p < d->n_pairs; ++p) {
@@ -1251,6 +1255,52 @@ int osot_kinematics(osot_kin* k, const osot_kin_batch* b, void* hip_stream) {
         if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 64>), grid, block, 0, st, dk, *b);
         else hipLaunchKernelGGL((osot_kin_kernel<false, 64>), grid, block, 0, st, dk, *b);
     }
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// batched rigid-body dynamics producer (osot_dyn.h): M(q), h(q, qdot), Jdot qdot of frames and of the centre of mass
+struct osot_dyn {
+    DevDyn* dev;
+    osot_kin_desc tree;
+    int device;
+};
+
+int osot_dyn_create(const osot_kin_desc* tree, const osot_dyn_desc* inertia, int device, osot_dyn** out) {
+    if (!tree || !inertia || !out) return fail(OSOT_ERR_INVALID, "null argument");
+    std::vector<DevDyn> image(1);    // (70 KB: not on the stack)
+    DevDyn& h = image[0];
+    const char* why = "";
+    const int rc = dyn_build(tree, inertia, h, &why);
+    if (rc != OSOT_OK) return fail(rc, why);
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    osot_dyn* d = new osot_dyn();
+    d->tree = h.k.d; d->device = device; d->dev = nullptr;
+    hipError_t e = hipMalloc(&d->dev, sizeof(DevDyn));
+    if (e == hipSuccess) e = hipMemcpy(d->dev, &h, sizeof(DevDyn), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { if (d->dev) hipFree(d->dev); delete d; return fail(OSOT_ERR_HIP, hipGetErrorString(e)); }
+    *out = d;
+    return OSOT_OK;
+}
+
+int osot_dyn_destroy(osot_dyn* d) {
+    if (!d) return OSOT_OK;
+    DeviceGuard guard(d->device);
+    if (d->dev) hipFree(d->dev);
+    delete d;
+    return OSOT_OK;
+}
+
+int osot_dynamics(osot_dyn* d, const osot_dyn_batch* b, void* hip_stream) {
+    if (!d || !b) return fail(OSOT_ERR_INVALID, "null argument");
+    const char* why = "";
+    const int rc = dyn_check_batch(d->tree, b, &why);
+    if (rc != OSOT_OK) return fail(rc, why);
+    if (b->B == 0) return OSOT_OK;
+    DeviceGuard guard(d->device);
+    if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    hipLaunchKernelGGL((osot_dyn_kernel<64>), dim3((unsigned)b->B), dim3(64), 0, (hipStream_t)hip_stream, (const DevDyn*)d->dev, *b, dyn_kin_batch(*b));
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

@@ -17,8 +17,85 @@ def _t(a, device):
     return torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(device)
 
 
+class Dynamics:
+    """osot_dyn handle (include/osot_mi355x.h: osot_dyn_create / osot_dynamics): inertia matrix, non-linear term, Jdot qdot of the
+    model's frames and of the centre of mass for a batch of postures, written in place into device tensors.  Mirrors
+    kinematics.Kinematics; the arithmetic is in csrc/osot_dyn.h."""
+
+    def __init__(self, model, device=0, gravity=(0.0, 0.0, -9.81)):
+        self.model = model
+        self._lib = abi.lib()
+        self._h = C.c_void_p()
+        kd, dd = model.desc(), abi.DynDesc()
+        I = np.zeros((model.n, 6)) if getattr(model, "inertia", None) is None else np.asarray(model.inertia, dtype=float).reshape(model.n, 6)
+        for j in range(model.n):
+            for i in range(6):
+                dd.inertia[j][i] = float(I[j, i])
+        for i in range(3):
+            dd.gravity[i] = float(gravity[i])
+        abi.check(self._lib.osot_dyn_create(C.byref(kd), C.byref(dd), int(device), C.byref(self._h)), "osot_dyn_create")
+        self.device = torch.device("cuda", device)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                self._lib.osot_dyn_destroy(self._h)
+                self._h = C.c_void_p()
+        except Exception:
+            pass
+
+    def batch_args(self, q, qdot=None, M=None, h=None, frame_jdotqdot=None, com_jdotqdot=None):
+        """the osot_dyn_batch of a call (pointers and strides; the tensors must outlive its use).  q, qdot [B][n] (device, qdot
+        may be None); M: a tensor whose leading dimension is the batch and whose instances start with the n x n matrix (IdModel.Bm,
+        or anything wider: the stride is its row length); h [B][n]; frame_jdotqdot: {frame index: tensor [B][6]} or
+        {frame index: (tensor [B][w], first column)} -- e.g. a task's leaf array p1; com_jdotqdot: tensor [B][>= 3] or (tensor, column)"""
+        B, n = q.shape
+        assert n == self.model.n and q.is_contiguous() and q.dtype == torch.float64
+        b = abi.DynBatch()
+        b.B, b.q = B, q.data_ptr()
+        if qdot is not None:
+            assert qdot.shape == q.shape and qdot.is_contiguous() and qdot.dtype == torch.float64
+            b.qdot = qdot.data_ptr()
+        if M is not None:
+            assert M.is_contiguous() and M.shape[0] >= B and M[0].numel() >= n * n
+            b.M, b.M_stride = M.data_ptr(), M[0].numel()
+        if h is not None:
+            assert h.is_contiguous() and h.shape[0] >= B and h.shape[1] == n
+            b.h = h.data_ptr()
+
+        def place(t, width):
+            t, col = t if isinstance(t, tuple) else (t, 0)
+            assert t.is_contiguous() and t.dim() == 2 and t.shape[0] >= B and col + width <= t.shape[1]
+            return t.data_ptr() + 8 * col, t.shape[1]
+        for f, t in (frame_jdotqdot or {}).items():
+            b.frame_Jdot_qdot[f], b.frame_Jdot_qdot_stride[f] = place(t, 6)
+        if com_jdotqdot is not None:
+            b.com_Jdot_qdot, b.com_Jdot_qdot_stride = place(com_jdotqdot, 3)
+        return b
+
+    def forward(self, q, qdot=None, M=None, h=None, frame_jdotqdot=None, com_jdotqdot=None):
+        """osot_dynamics, stream-ordered on torch's current stream"""
+        b = self.batch_args(q, qdot, M, h, frame_jdotqdot, com_jdotqdot)
+        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        abi.check(self._lib.osot_dynamics(self._h, C.byref(b), stream), "osot_dynamics")
+
+
 class IdModel:
     """B [B][nv][nv], h [B][nv], Jc [B][contacts][3 or 6][nv]; x = [qddot; forces] (InverseDynamics.cpp:12-28)"""
+
+    @classmethod
+    def empty(cls, B, nv, n_contacts, contact_dim=6, device=0, floating_base=True):
+        """a model on zeroed device tensors that the producers fill IN PLACE every cycle: Bm and h by Dynamics.forward(M=model.Bm,
+        h=model.h), Jc by Kinematics.forward(frame_J={frame: model.contact_rows(c)}) -- IdModel keeps the tensors it is given when
+        they already are float64 on its device, so write_rows / computed_torque read what the producers wrote"""
+        dev = torch.device("cuda", device)
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=dev)
+        return cls(z(B, nv, nv), z(B, nv), z(B, n_contacts, contact_dim, nv), device=device, floating_base=floating_base)
+
+    def contact_rows(self, c):
+        """(tensor [B][n_contacts * contact_dim][nv], first row) of contact c: the frame_J binding of kinematics.Kinematics"""
+        assert self.cdim == 6, "the kinematics producer writes the six rows of a frame's Jacobian"
+        return self.Jc.view(self.B, self.n_contacts * self.cdim, self.nv), c * self.cdim
 
     def __init__(self, Bm, h, Jc, device=0, floating_base=True):
         self.device = torch.device("cuda", device)
@@ -68,6 +145,74 @@ class IdModel:
         abi.check(self._lib.osot_computed_torque(C.byref(m), C.c_void_p(x.data_ptr()), C.c_void_p(tau.data_ptr()),
                                                  C.c_void_p(ok.data_ptr()), fb_tol, st), "osot_computed_torque")
         return tau, ok
+
+
+class IdStep:
+    """One device-resident inverse-dynamics control step of a stack made by synth.make_coman_id_stack:
+        q, qdot -> osot_kinematics + osot_dynamics -> leaf errors -> osot_id_rows -> osot_cycle -> osot_computed_torque -> integrate
+    produce() runs the two producer launches; consume() everything behind them, reading ONLY the tensors the producers fill
+    (model.Bm / h / Jc, Jcom, com, jdq, com_jdq) -- so a caller may fill those from another source instead (the tests upload
+    host-computed quantities).  Every launch goes to torch's current stream; nothing allocates after the constructor, so step()
+    can be captured into a graph."""
+
+    def __init__(self, plan, leaf, kin_model, device=0, dt=1.0e-3, gravity=(0.0, 0.0, -9.81)):
+        from .kinematics import Kinematics
+        from .solver import BatchedStack
+        B, nv = leaf["B"], leaf["nv"]
+        self.B, self.nv, self.dt, self.plan = B, nv, dt, plan
+        self.st = BatchedStack(plan, B, device=device)
+        self.dev = self.st.load_leaf(leaf)
+        d = self.st.device
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(d)
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=d)
+        self.q, self.qdot, self.q_ref = t(leaf["state"]["q0"]), t(leaf["state"]["qdot0"]), t(leaf["state"]["q_ref"])
+        self.kin, self.dyn = Kinematics(kin_model, device), Dynamics(kin_model, device, gravity)
+        self.frames = [kin_model.frame_index(c) for c in leaf["contacts"]]
+        self.model = IdModel.empty(B, nv, len(self.frames), 6, device=device)
+        self.Jcom, self.com, self.com_ref = z(B, 3, nv), z(B, 3), None
+        # the leaves the producers write straight into: Jdot qdot of the contact tasks and of the CoM task (p1), h of the torque limits (p0)
+        (self.p0_l, self.jdq_l, _), (self.p0_r, self.jdq_r, _), (self.p0_com, self.jdq_com, _) = self.dev["task"][0]
+        self.p0_post = self.dev["task"][1][0][0]
+        self.h_u = self.dev["rows"][0][0]
+        self.dev["rows"][3] = (self.model.h, self.dev["rows"][3][1], None)
+        self.J12 = self.model.Jc.view(B, 12, nv)
+        self.tau, self.ok = z(B, nv), torch.zeros((B,), dtype=torch.int32, device=d)
+        self._mc = self.model._c()
+        self._lib = abi.lib()
+
+    def produce(self):
+        self.kin.forward(self.q, frame_J={f: self.model.contact_rows(c) for c, f in enumerate(self.frames)}, com=self.com,
+                         com_J=(self.Jcom, 0))
+        self.dyn.forward(self.q, self.qdot, M=self.model.Bm, h=self.model.h,
+                         frame_jdotqdot={self.frames[0]: self.jdq_l, self.frames[1]: self.jdq_r}, com_jdotqdot=self.jdq_com)
+
+    def consume(self):
+        nv, dt = self.nv, self.dt
+        if self.com_ref is None:
+            self.com_ref = self.com.clone()
+        # leaf errors (what the tasks' _update() computes): CoM and postural; the contact tasks ask for zero acceleration
+        self.p0_com[:, :3] = self.com_ref - self.com
+        self.p0_com[:, 3:] = -(self.Jcom * self.qdot[:, None, :]).sum(dim=2)
+        self.p0_post[:, :nv] = self.q_ref - self.q
+        self.p0_post[:, nv:] = -self.qdot
+        self.h_u.copy_(self.model.h[:, :6])
+        self.model.write_rows(self.st, dyn_block=0, tau_block=3, tasks=[(0, 0, self.J12), (0, 12, self.Jcom)])
+        self.st.cycle(self.dev)
+        x = self.st.dq[:self.B]
+        stream = C.c_void_p(torch.cuda.current_stream(self.st.device).cuda_stream)
+        abi.check(self._lib.osot_computed_torque(C.byref(self._mc), C.c_void_p(x.data_ptr()), C.c_void_p(self.tau.data_ptr()),
+                                                 C.c_void_p(self.ok.data_ptr()), 10e-3, stream), "osot_computed_torque")
+
+    def integrate(self):
+        qdd = self.st.dq[:self.B, :self.nv]
+        self.q.add_(self.qdot, alpha=self.dt).add_(qdd, alpha=0.5 * self.dt * self.dt)
+        self.qdot.add_(qdd, alpha=self.dt)
+
+    def step(self, producers=True):
+        if producers:
+            self.produce()
+        self.consume()
+        self.integrate()
 
 
 def force_gains(J, Bi, Kp, Kd, p0, rows, f_virtual=None, a_ref=None):

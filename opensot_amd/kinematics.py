@@ -41,6 +41,9 @@ class KinModel:
     env_shapes: list = field(default_factory=list)
     self_pairs: list = None
     env_links: list = field(default_factory=list)
+    # rotational inertia [n][6] (Ixx Ixy Ixz Iyy Iyz Izz) of the link every joint moves, about its centre of mass, axes of the joint
+    # frame (osot_dyn_desc.inertia: the dynamics producer, opensot_amd/dynamics.py); None = point masses
+    inertia: np.ndarray = None
 
     # ---- the reference's three calls ------------------------------------------------------------------------------
     def add_collision_shape(self, name, link, shape, link_T_shape=None):
@@ -252,7 +255,7 @@ def humanoid32_pairs(m):
     return m
 
 
-def from_json(path):
+def from_json(path, inertia_path=None):
     """a tree fixture as written by tests/golden/make_coman_tree.py (the reference's COMAN, 6 virtual + 29 revolute
     joints): returns (KinModel, lower[n], upper[n]) -- the limits are +-inf for the virtual joints."""
     import json
@@ -263,6 +266,11 @@ def from_json(path):
                  p0=np.array([j["p0"] for j in J], dtype=float), mass=np.array([j["mass"] for j in J], dtype=float),
                  com=np.array([j["com"] for j in J], dtype=float), names=[j["name"] for j in J])
     m.frames = [(f["name"], f["joint"], np.array(f["R"], dtype=float).reshape(3, 3), tuple(f["p"])) for f in d["frames"]]
+    # optional rotational inertia [n][6] about the links' centres of mass: an "inertia" entry of the tree file, or of a file of its
+    # own (tests/golden/coman_inertia.json, written by make_coman_inertia.py)
+    di = json.load(open(inertia_path)) if inertia_path is not None else d
+    if "inertia" in di:
+        m.inertia = np.array(di["inertia"], dtype=float).reshape(len(J), 6)
     lo = np.array([-np.inf if j["lower"] is None else j["lower"] for j in J])
     up = np.array([np.inf if j["upper"] is None else j["upper"] for j in J])
     return m, lo, up

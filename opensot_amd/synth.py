@@ -200,6 +200,7 @@ def make_id_stack(B, seed=None, nv=38, n_contacts=4, eps_factor=1e6, torque_limi
     rows   : DynamicFeasibility (6 eq) [B_u, -J_f'], FrictionCone (5 per contact), TorqueLimits (nv) [B, -Jc'],
              acceleration::JointLimits (nv unit rows), acceleration::VelocityLimits (nv unit rows)
     Model quantities (B, h, J, Jdot*qdot) are synthetic: B = L L' + I, h ~ N(0, 5^2), J ~ N(0, 0.3^2).
+    (make_coman_id_stack is the stack whose model quantities come from the device producers.)
     The stack is feasible by construction around qddot = 0 with supporting contact forces.
     """
     rng = np.random.default_rng(5000 if seed is None else seed)
@@ -657,3 +658,56 @@ def make_wide_robot_stack(B, n=96, levels=3, seed=0, eps_factor=1e6, n_ineq=16, 
         rleaf.append((Cl, -rng.uniform(0.002, 0.02, size=(B, n_local)), rng.uniform(0.002, 0.02, size=(B, n_local))))
     plan = StackPlan(n=n, levels=plan_levels, bounds=bounds, rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
     return plan, {"B": B, "A": A, "task": tleaf, "bound": bleaf, "rows": rleaf}
+
+
+def make_coman_id_stack(B, seed=None, tree=None, inertia=None, eps_factor=1e6):
+    """Floating-base inverse dynamics of the reference's COMAN (35 coordinates) standing on both soles as SURFACE contacts:
+    x = [qddot (35); wrench l_sole (6); wrench r_sole (6)], n = 47 (wavefront route).  The MODEL QUANTITIES ARE LEFT FOR THE PRODUCERS
+    (opensot_amd.dynamics.IdStep: osot_kinematics + osot_dynamics every step); the leaf carries references, limits and the state.
+
+    levels : 0 = acceleration::Contact on l_sole and r_sole (6 rows each: J qddot = -Jdot qdot) + acceleration::CoM (3)
+             1 = acceleration::Postural on the 35 coordinates
+    rows   : DynamicFeasibility (6), force::FrictionCone on the two wrenches (10), force::CoP (8), TorqueLimits (35)
+    The posture is a standing one, knees bent, soles flat, at rest; the postural reference moves the arms and the waist by a few
+    hundredths of a radian, so the robot moves while the wrenches stay well inside the cones and the CoP rectangles (the contact
+    frame of cones and CoP is the ground: identity).  Returns (plan, leaf, model); leaf["state"] = q0, qdot0, q_ref."""
+    import os
+    from . import kinematics as kin
+    here = os.path.dirname(os.path.abspath(__file__))
+    gold = os.path.join(os.path.dirname(here), "tests", "golden")
+    model, lo, up = kin.from_json(tree or os.path.join(gold, "coman_tree.json"), inertia or os.path.join(gold, "coman_inertia.json"))
+    rng = np.random.default_rng(9000 if seed is None else seed)
+    nv, nf = model.n, 12
+    n = nv + nf
+    ix = model.names.index
+    q0 = np.zeros((B, nv))
+    for s_ in "LR":
+        q0[:, ix(s_ + "HipSag")] = -0.3; q0[:, ix(s_ + "KneeSag")] = 0.6; q0[:, ix(s_ + "AnkSag")] = -0.3
+        q0[:, ix(s_ + "Elbj")] = -0.8; q0[:, ix(s_ + "ShSag")] = 0.2
+    q0[:, ix("LShLat")] = 0.3; q0[:, ix("RShLat")] = -0.3
+    upper = list(range(ix("WaistLat"), ix("RHipSag")))          # waist and arms
+    q0[:, upper] += rng.normal(0.0, 0.02, (B, len(upper)))
+    q0 = np.clip(q0, np.maximum(lo, -10.0) + 1e-3, np.minimum(up, 10.0) - 1e-3)
+    q_ref = q0.copy()
+    q_ref[:, upper] += rng.uniform(-0.05, 0.05, (B, len(upper)))
+    z = lambda *sh: np.zeros(sh)
+    levels = [[Task(abi.TASK_ACC_CARTESIAN, 6, lam=0.0, lam2=0.0, name="l_sole_contact"),
+               Task(abi.TASK_ACC_CARTESIAN, 6, lam=0.0, lam2=0.0, name="r_sole_contact"),
+               Task(abi.TASK_ACC_COM, 3, lam=25.0, lam2=10.0, name="com")],
+              [Task(abi.TASK_ACC_POSTURAL, nv, lam=25.0, lam2=10.0, name="postural")]]
+    tleaf = [[(z(B, 12), z(B, 6), None), (z(B, 12), z(B, 6), None), (z(B, 6), z(B, 3), None)],
+             [(np.concatenate([q_ref - q0, z(B, nv)], axis=1), None, None)]]
+    R9 = np.tile(np.eye(3).reshape(9), (B, 2, 1))
+    lims = np.tile(np.array([-0.06, 0.12, -0.045, 0.045]), (B, 2, 1))       # the sole rectangle around the sole frame's origin
+    tau_max = np.full((B, nv), 60.0)
+    tau_max[:, :6] = 1.0e3                                      # floating-base rows: the equality handles them
+    mu = 0.8
+    rowblocks = [Rows(abi.ROWS_DYN_FEASIBILITY, 6, name="dynamic_feasibility"),
+                 Rows(abi.ROWS_WRENCH_FRICTION_CONE, 10, first_col=nv, mu=mu, name="friction_cones"),
+                 Rows(abi.ROWS_COP, 8, first_col=nv, name="cop"),
+                 Rows(abi.ROWS_TORQUE_LIMITS, nv, name="torque_limits")]
+    rleaf = [(z(B, 6), None, None), (R9, None, None), (R9, lims, None), (z(B, nv), tau_max, None)]
+    plan = StackPlan(n=n, levels=levels, bounds=[], rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, 15, n), None], "task": tleaf, "bound": [], "rows": rleaf, "C": [None] * 4,
+            "state": {"q0": q0, "qdot0": z(B, nv), "q_ref": q_ref}, "contacts": ("l_sole", "r_sole"), "nv": nv}
+    return plan, leaf, model
