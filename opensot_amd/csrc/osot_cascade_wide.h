@@ -18,7 +18,7 @@
 // The body is written against the two-member team of osot_qp_big.h, so the same source compiles for the host (tests/emu).
 #pragma once
 #include <cstring>
-#include <osot_mi355x.h>
+#include "osot_plan_shape.h"
 #include "osot_qp_big.h"
 
 namespace osot {
@@ -52,53 +52,14 @@ struct Batch {
     int *status, *iterations;
     double* work;                       // [grid][2][n][n]
 };
-
-// a Postural block has A = [I 0] (Postural.cpp:37): implicit, never stored -- unless it is a SubTask or has a dense weight
-inline bool implicit_task(const osot_task_desc& t) {
-    return (t.kind == OSOT_TASK_POSTURAL || t.kind == OSOT_TASK_ACC_POSTURAL) && t.row_mask == 0ull && !t.dense_weight;
-}
-inline bool implicit_rows(int kind) {
-    return kind == OSOT_ROWS_ACC_JOINT_LIMITS || kind == OSOT_ROWS_ACC_VELOCITY_LIMITS || kind == OSOT_ROWS_UNIT_GENERIC;
-}
+static_assert(std::is_trivially_copyable<Plan>::value && std::is_trivially_copyable<Batch>::value, "kernel arguments, zeroed with memset");
 
 // host side: the plan (and the call's level / task switches) -> kernel argument
 inline void make_plan(const osot_plan_desc& p, const unsigned char* level_active, const unsigned char* task_active, Plan& P) {
     std::memset(&P, 0, sizeof(P));
-    P.n = p.n; P.L = p.n_levels;
-    int off = 0, soff = 0;
-    P.nblocks = p.n_rowblocks;
-    for (int j = 0; j < p.n_rowblocks; ++j) {
-        const osot_rows_desc& rb = p.rowblock[j];
-        P.blk_rows[j] = rb.rows; P.blk_off[j] = off; P.blk_stored_off[j] = soff;
-        P.blk_implicit[j] = implicit_rows(rb.kind) ? 1 : 0;
-        P.blk_first_col[j] = rb.first_col; P.blk_level[j] = rb.only_level;
-        off += rb.rows;
-        if (!P.blk_implicit[j]) soff += rb.rows;
-    }
-    P.nc = off; P.nc_stored = soff;
-    P.optoff[0] = 0;
-    for (int k = 0; k < p.n_levels; ++k) {
-        const osot_level_desc& lv = p.level[k];
-        int m = 0, ma = 0;
-        P.ntask[k] = lv.n_tasks;
-        for (int j = 0; j < lv.n_tasks; ++j) {
-            P.task_off[k][j] = m;
-            m += lv.task[j].rows;
-            if (!implicit_task(lv.task[j])) ma += lv.task[j].rows;
-            if (task_active && !task_active[k * OSOT_MAX_TASKS + j]) P.inactive[k] |= (1u << j);
-        }
-        P.task_off[k][lv.n_tasks] = m;
-        P.m[k] = m; P.ma[k] = ma;
-        P.optoff[k + 1] = P.optoff[k] + m;
-        if (!level_active || level_active[k]) P.active_mask |= (1u << k);
-    }
+    make_plan_shape(p, level_active, task_active, P);
     P.nrows = P.nc + P.optoff[p.n_levels - 1];
     P.big_bytes = (int)((big::shared_bytes(p.n, P.nrows) + 15) & ~(size_t)15);
-    P.max_iter = p.max_iter > 0 ? p.max_iter : 20 * (p.n + P.nc + P.optoff[p.n_levels]) + 100;   // (the wavefront route's cap, make_dev_plan)
-    P.eps_abs = p.eps_abs;
-    P.reg_rows = p.has_regularisation ? p.regularisation.rows : 0;
-    P.reg_w = p.has_regularisation ? p.regularisation.weight : 0.0;
-    P.reg_dense = (p.has_regularisation && p.regularisation_dense) ? 1 : 0;
 }
 
 // LDS of one workgroup: the solver's (big::shared_bytes for the table's capacity), then x_prev, x_k, g, the box (relaxed where a level

@@ -21,7 +21,7 @@
 // column: the halves split every inner product), NP = 64 for n <= 64.  Instance-major fp64 arrays, so a
 // wave's reads of its stacked Jacobian rows are contiguous 8n-byte segments.
 #pragma once
-#include <osot_mi355x.h>   // OSOT_MAX_* (the C-ABI's limits are the kernels' limits)
+#include "osot_plan_shape.h"   // OSOT_KMAX_*, make_plan_shape, fill_batch_ptrs
 #include "osot_qp_core.h"
 
 #ifndef OSOT_WAVES32
@@ -33,15 +33,10 @@
 #ifndef OSOT_WAVES40
 #define OSOT_WAVES40 2   // waves per SIMD the NP = 40 instantiations (33 .. 38 variables) are compiled for
 #endif
-#define OSOT_KMAX_LEVELS 8
-#define OSOT_KMAX_TASKS 8
-#define OSOT_KMAX_FLAT_TASKS 24
-#define OSOT_KMAX_BOUNDS 4
-#define OSOT_KMAX_ROWBLOCKS 8
-#define OSOT_KMAX_FLAT_ROWS 256
 
 namespace osot {
 
+// (make_plan_shape / fill_batch_ptrs of osot_plan_shape.h fill the members the workgroup route's wide::Plan / wide::Batch name alike)
 struct DevPlan {
     int n, L, nc;
     int m[OSOT_KMAX_LEVELS];        // rows per level
@@ -106,6 +101,7 @@ struct DevBatch {
                               // with (constraint codes, -1 = none), read at the start of a level and rewritten at its end
                               // (gi_inequalities); null: cold start, nothing recorded
 };
+static_assert(std::is_trivially_copyable<DevPlan>::value && std::is_trivially_copyable<DevBatch>::value, "kernel arguments, zeroed with memset");
 
 // Row table of level k (LDS): [ global C rows ; A_0 ; ... ; A_{k-1} ]  (iHQP.cpp:282-333).  The C entries are
 // filled once per instance, the optimality entries of level j are appended when level j has been solved

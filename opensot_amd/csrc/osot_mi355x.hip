@@ -202,9 +202,9 @@ int osot_plan_validate_wide(const osot_plan_desc* plan) {
     const char* why;
     int rc = plan_validate(plan, &why, 1);
     if (rc != OSOT_OK) return fail(rc, why);
-    if (wide::shared_bytes(plan->n, [&] { int nc = 0, rows = 0; plan_constraint_rows(plan, &nc);
-                                          for (int k = 0; k + 1 < plan->n_levels; ++k) { int m = 0; plan_level_rows(plan, k, &m, nullptr); rows += m; }
-                                          return nc + rows; }()) > 160 * 1024)
+    wide::Plan P;
+    wide::make_plan(*plan, nullptr, nullptr, P);
+    if (wide::shared_bytes(plan->n, P.nrows) > 160 * 1024)
         return fail(OSOT_ERR_UNSUPPORTED, "wide route: the row table of this plan does not fit the 160 KiB LDS of a CU");
     return OSOT_OK;
 }
@@ -220,6 +220,33 @@ int osot_plan_stored_constraint_rows(const osot_plan_desc* plan, int* nc_stored)
     int rc = plan_stored_constraint_rows(plan, nc_stored);
     return rc == OSOT_OK ? rc : fail(rc, "bad plan");
 }
+
+}  // extern "C"
+
+// what the two routes' constructors share: the handle with its plan and the host copy of the update plan ...
+static osot_solver* solver_new(const osot_plan_desc& plan, int max_batch, int device) {
+    osot_solver* s = new osot_solver();
+    s->plan = plan;
+    s->max_batch = max_batch;
+    s->device = device;
+    s->timing = false;
+    std::memset(s->task_active, 1, sizeof(s->task_active));
+    make_update_plan(plan, s->h_uplan);
+    return s;
+}
+// ... and, after the route's own allocations (allocated: they succeeded), the update plan's upload.  The static update plan lives
+// with the solver from the start (no lazy allocation on whatever device is current).  One clean-up path: osot_solver_destroy
+static int solver_finish(osot_solver* s, bool allocated, osot_solver** out) {
+    if (!allocated || hipMalloc(&s->d_uplan, sizeof(DevUpdatePlan)) != hipSuccess ||
+        hipMemcpy(s->d_uplan, &s->h_uplan, sizeof(DevUpdatePlan), hipMemcpyHostToDevice) != hipSuccess) {
+        osot_solver_destroy(s);
+        return fail(OSOT_ERR_HIP, "device allocation for the solver failed");
+    }
+    *out = s;
+    return OSOT_OK;
+}
+
+extern "C" {
 
 int osot_solver_create(const osot_plan_desc* plan, int max_batch, int device, osot_solver** out) {
     if (!out) return fail(OSOT_ERR_INVALID, "null out");
@@ -262,12 +289,7 @@ int osot_solver_create(const osot_plan_desc* plan, int max_batch, int device, os
         return r;
     });
     if (rc != OSOT_OK) return rc;
-    osot_solver* s = new osot_solver();
-    s->plan = *plan;
-    s->max_batch = max_batch;
-    s->device = device;
-    s->timing = false;
-    std::memset(s->task_active, 1, sizeof(s->task_active));
+    osot_solver* s = solver_new(*plan, max_batch, device);
     {   // resident workgroups: what the longest-first dispatch order is planned for (order_body)
         int per_cu = 0, cus = 0;
         hipError_t e1 = by_np(T, [&](auto np) {
@@ -277,31 +299,21 @@ int osot_solver_create(const osot_plan_desc* plan, int max_batch, int device, os
         s->slots = (e1 == hipSuccess && e2 == hipSuccess && per_cu > 0 && cus > 0) ? per_cu * cus : 2048;
     }
     if (P.rows_in_global && hipMalloc(&s->d_rows, sizeof(double) * (size_t)max_batch * (size_t)P.rows_doubles) != hipSuccess) {
-        delete s;
+        osot_solver_destroy(s);
         return fail(OSOT_ERR_HIP, "device allocation for the row tables failed");
     }
-    make_update_plan(*plan, s->h_uplan);
-    // dispatch-order state and the static update plan live with the solver from the start (no lazy allocation on
-    // whatever device is current)
-    if (hipMalloc(&s->d_cost, sizeof(int) * 2 * (size_t)max_batch) != hipSuccess ||
-        hipMemset(s->d_cost, 0, sizeof(int) * 2 * (size_t)max_batch) != hipSuccess ||
-        hipMalloc(&s->d_order, sizeof(int) * 2 * (size_t)max_batch) != hipSuccess ||
+    // the dispatch-order state lives with the solver from the start too
+    const bool allocated =
+        hipMalloc(&s->d_cost, sizeof(int) * 2 * (size_t)max_batch) == hipSuccess &&
+        hipMemset(s->d_cost, 0, sizeof(int) * 2 * (size_t)max_batch) == hipSuccess &&
+        hipMalloc(&s->d_order, sizeof(int) * 2 * (size_t)max_batch) == hipSuccess &&
         [&] {   // both halves of the order buffer start as the identity permutation: a half that no launch has written yet
                 // (a graph capture that failed half-way leaves the host-side flip ahead of the device) is still a valid order
             std::vector<int> id(2 * (size_t)max_batch);
             for (int i = 0; i < 2 * max_batch; ++i) id[i] = i % max_batch;
-            return hipMemcpy(s->d_order, id.data(), sizeof(int) * id.size(), hipMemcpyHostToDevice) != hipSuccess;
-        }() ||
-        hipMalloc(&s->d_uplan, sizeof(DevUpdatePlan)) != hipSuccess ||
-        hipMemcpy(s->d_uplan, &s->h_uplan, sizeof(DevUpdatePlan), hipMemcpyHostToDevice) != hipSuccess) {
-        if (s->d_cost) hipFree(s->d_cost);
-        if (s->d_order) hipFree(s->d_order);
-        if (s->d_uplan) hipFree(s->d_uplan);
-        delete s;
-        return fail(OSOT_ERR_HIP, "device allocation for the solver failed");
-    }
-    *out = s;
-    return OSOT_OK;
+            return hipMemcpy(s->d_order, id.data(), sizeof(int) * id.size(), hipMemcpyHostToDevice) == hipSuccess;
+        }();
+    return solver_finish(s, allocated, out);
 }
 
 int osot_solver_create_wide(const osot_plan_desc* plan, int max_batch, int device, osot_solver** out) {
@@ -321,27 +333,12 @@ int osot_solver_create_wide(const osot_plan_desc* plan, int max_batch, int devic
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_cascade_wide_kernel, 256, lds));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     if (per_cu < 1 || cus < 1) return fail(OSOT_ERR_UNSUPPORTED, "the wide cascade kernel does not fit a CU for this plan");
-    osot_solver* s = new osot_solver();
-    s->plan = *plan;
-    s->max_batch = max_batch;
-    s->device = device;
-    s->timing = false;
+    osot_solver* s = solver_new(*plan, max_batch, device);
     s->wide = 1;
     s->wide_lds = lds;
     s->slots = per_cu * cus;
     s->wide_grid = max_batch < s->slots ? max_batch : s->slots;
-    std::memset(s->task_active, 1, sizeof(s->task_active));
-    make_update_plan(*plan, s->h_uplan);
-    if (hipMalloc(&s->d_work, sizeof(double) * 2 * (size_t)P.n * P.n * (size_t)s->wide_grid) != hipSuccess ||
-        hipMalloc(&s->d_uplan, sizeof(DevUpdatePlan)) != hipSuccess ||
-        hipMemcpy(s->d_uplan, &s->h_uplan, sizeof(DevUpdatePlan), hipMemcpyHostToDevice) != hipSuccess) {
-        if (s->d_work) hipFree(s->d_work);
-        if (s->d_uplan) hipFree(s->d_uplan);
-        delete s;
-        return fail(OSOT_ERR_HIP, "device allocation for the solver failed");
-    }
-    *out = s;
-    return OSOT_OK;
+    return solver_finish(s, hipMalloc(&s->d_work, sizeof(double) * 2 * (size_t)P.n * P.n * (size_t)s->wide_grid) == hipSuccess, out);
 }
 
 int osot_solver_destroy(osot_solver* s) {
@@ -435,7 +432,7 @@ int osot_ehqp_solve(osot_solver* s, const osot_qp_batch* b, double sigma_min, vo
     if (s->wide) return refuse_wide(s, "the eHQP front-end");
     if (b->B < 0 || b->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
     if (b->B == 0) return OSOT_OK;
-    if (!b->dq || !b->status) return fail(OSOT_ERR_INVALID, "dq/status output is null");
+    if (const char* w = outputs_missing(*b)) return fail(OSOT_ERR_INVALID, w);
     const osot_plan_desc& pl = s->plan;
     DevEhqp Q;
     const char* why = "";
@@ -462,7 +459,7 @@ int osot_nhqp_solve(osot_solver* s, const osot_qp_batch* b, const osot_nhqp_opti
     if (s->wide) return refuse_wide(s, "the nHQP front-end");
     if (b->B < 0 || b->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
     if (b->B == 0) return OSOT_OK;
-    if (!b->dq || !b->status) return fail(OSOT_ERR_INVALID, "dq/status output is null");
+    if (const char* w = outputs_missing(*b)) return fail(OSOT_ERR_INVALID, w);
     DeviceGuard guard(s->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
     const osot_plan_desc& pl = s->plan;
@@ -475,12 +472,11 @@ int osot_nhqp_solve(osot_solver* s, const osot_qp_batch* b, const osot_nhqp_opti
         if (rc != OSOT_OK) return fail(rc, why);
         for (int k = 0; k < pl.n_levels; ++k) {
             int m, ma; plan_level_rows(&pl, k, &m, &ma);
-            if (ma > 0 && !b->A[k]) return fail(OSOT_ERR_INVALID, "A[k] is null for a level with stored rows");
-            if (!b->b[k]) return fail(OSOT_ERR_INVALID, "b[k] is null");
+            if (const char* w = level_ptrs_missing(*b, k, ma, false)) return fail(OSOT_ERR_INVALID, w);
         }
         int nc = 0; plan_constraint_rows(&pl, &nc);
         if (nc > 0 && (!b->C || !b->lo || !b->up)) return fail(OSOT_ERR_INVALID, "plan has constraint rows but C/lo/up is null");
-        if (pl.n_bounds > 0 && (!b->l || !b->u)) return fail(OSOT_ERR_INVALID, "plan has bounds but l/u is null");
+        if (const char* w = bounds_missing(pl, *b)) return fail(OSOT_ERR_INVALID, w);
     }
     if (!s->nhqp_ready) {
         const NhqpSizes z = nhqp_sizes(pl, s->max_batch);
@@ -614,6 +610,25 @@ int osot_solver_profile_phases(osot_solver* s, const osot_qp_batch* b, long long
     return ihqp_launch(s, b, hip_stream, cycles);
 }
 
+// the event bracket of a timed launch (osot_solver_set_timing: every timing_stride-th one): timed_begin takes a pair from the pool
+// and records its first event, timed_end records the second and queues the pair for osot_solver_kernel_time_ms.  timed_begin
+// comes after the LAST early return of a launch function
+struct TimedLaunch { bool timed = false; std::pair<hipEvent_t, hipEvent_t> ev; };
+static int timed_begin(osot_solver* s, hipStream_t st, TimedLaunch& t) {
+    t.timed = s->timing && (s->timing_count++ % s->timing_stride) == 0;
+    if (!t.timed) return OSOT_OK;
+    if (!s->pool.empty()) { t.ev = s->pool.back(); s->pool.pop_back(); }
+    else { HIP_TRY(hipEventCreate(&t.ev.first)); HIP_TRY(hipEventCreate(&t.ev.second)); }
+    HIP_TRY(hipEventRecord(t.ev.first, st));
+    return OSOT_OK;
+}
+static int timed_end(osot_solver* s, hipStream_t st, const TimedLaunch& t) {
+    if (!t.timed) return OSOT_OK;
+    HIP_TRY(hipEventRecord(t.ev.second, st));
+    s->events.push_back(t.ev);
+    return OSOT_OK;
+}
+
 // the workgroup route: osot_ihqp_solve, and osot_cycle as TWO launches on the stream (osot_update_kernel, then the cascade)
 static int wide_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control) {
     if (prof) return refuse_wide(s, "phase profiling");
@@ -623,49 +638,21 @@ static int wide_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
     wide::make_plan(pl, b->level_active, s->any_inactive ? s->task_active : nullptr, P);
     wide::Batch D;
     std::memset(&D, 0, sizeof(D));
-    D.B = b->B;
-    for (int k = 0; k < pl.n_levels; ++k) {
-        if (P.ma[k] > 0 && !b->A[k]) return fail(OSOT_ERR_INVALID, "A[k] is null for a level with stored rows");
-        if (!b->b[k]) return fail(OSOT_ERR_INVALID, "b[k] is null");
-        D.A[k] = b->A[k]; D.b[k] = b->b[k]; D.w[k] = b->w[k]; D.c[k] = b->c[k];
-        if (s->h_uplan.dense_level[k]) {
-            if (!b->WA[k] || !b->Wb[k]) return fail(OSOT_ERR_INVALID, "level has a non-diagonal weight but WA[k] / Wb[k] is null");
-            D.WA[k] = b->WA[k]; D.Wb[k] = b->Wb[k];
-        }
-    }
-    if (P.nc > 0 && (!b->lo || !b->up)) return fail(OSOT_ERR_INVALID, "plan has constraint rows but lo/up is null");
-    if (P.nc_stored > 0 && !b->C) return fail(OSOT_ERR_INVALID, "plan has stored constraint rows but C is null");
-    if (pl.n_bounds > 0 && (!b->l || !b->u)) return fail(OSOT_ERR_INVALID, "plan has bounds but l/u is null");
-    if (!b->dq || !b->status) return fail(OSOT_ERR_INVALID, "dq/status output is null");
-    if (pl.has_regularisation && !b->b_reg) return fail(OSOT_ERR_INVALID, "plan has a regularisation task but b_reg is null");
-    if (pl.has_regularisation && pl.regularisation_dense && !b->A_reg)
-        return fail(OSOT_ERR_INVALID, "the regularisation task has a stored Jacobian but A_reg is null");
-    D.C = P.nc_stored ? b->C : nullptr; D.lo = b->lo; D.up = b->up;
-    D.l = pl.n_bounds ? b->l : nullptr; D.u = pl.n_bounds ? b->u : nullptr;
-    D.b_reg = pl.has_regularisation ? b->b_reg : nullptr;
-    D.A_reg = (pl.has_regularisation && pl.regularisation_dense) ? b->A_reg : nullptr;
-    D.dq = b->dq; D.x_levels = b->x_levels; D.accepted_slack = b->accepted_slack;
-    D.status = b->status; D.iterations = b->iterations;
+    const char* why = "";
+    const int rc = fill_batch_ptrs(pl, P, *b, D, &why);
+    if (rc != OSOT_OK) return fail(rc, why);
     D.work = s->d_work;
     hipStream_t st = (hipStream_t)hip_stream;
     if (fused) {
         hipLaunchKernelGGL(osot_update_kernel, dim3((unsigned)b->B), dim3(64), 0, st, *fused);
         HIP_TRY(hipGetLastError());
     }
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool timed = s->timing && (s->timing_count++ % s->timing_stride) == 0;
-    if (timed) {
-        if (!s->pool.empty()) { ev = s->pool.back(); s->pool.pop_back(); }
-        else { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
-        HIP_TRY(hipEventRecord(ev.first, st));
-    }
+    TimedLaunch tl;
+    if (int r = timed_begin(s, st, tl)) return r;
     const unsigned grid = (unsigned)(b->B < s->wide_grid ? b->B : s->wide_grid);
     hipLaunchKernelGGL(osot_cascade_wide_kernel, dim3(grid), dim3(256), s->wide_lds, st, P, D);
     HIP_TRY(hipGetLastError());
-    if (timed) {
-        HIP_TRY(hipEventRecord(ev.second, st));
-        s->events.push_back(ev);
-    }
+    if (int r = timed_end(s, st, tl)) return r;
     return OSOT_OK;
 }
 
@@ -686,31 +673,10 @@ static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
     if (control && lds < control_kin_lds_bytes(T)) lds = control_kin_lds_bytes(T);
     DevBatch D;
     std::memset(&D, 0, sizeof(D));
-    D.B = b->B;
-    for (int k = 0; k < pl.n_levels; ++k) {
-        if (P.ma[k] > 0 && !b->A[k]) return fail(OSOT_ERR_INVALID, "A[k] is null for a level with stored rows");
-        if (!b->b[k]) return fail(OSOT_ERR_INVALID, "b[k] is null");
-        D.A[k] = b->A[k]; D.b[k] = b->b[k]; D.w[k] = b->w[k]; D.c[k] = b->c[k];
-        if (s->h_uplan.dense_level[k]) {
-            if (!b->WA[k] || !b->Wb[k]) return fail(OSOT_ERR_INVALID, "level has a non-diagonal weight but WA[k] / Wb[k] is null");
-            D.WA[k] = b->WA[k]; D.Wb[k] = b->Wb[k];
-        }
-    }
-    if (P.nc > 0 && (!b->lo || !b->up)) return fail(OSOT_ERR_INVALID, "plan has constraint rows but lo/up is null");
-    if (P.nc_stored > 0 && !b->C) return fail(OSOT_ERR_INVALID, "plan has stored constraint rows but C is null");
-    if (pl.n_bounds > 0 && (!b->l || !b->u)) return fail(OSOT_ERR_INVALID, "plan has bounds but l/u is null");
-    if (!b->dq || !b->status) return fail(OSOT_ERR_INVALID, "dq/status output is null");
-    D.C = P.nc_stored ? b->C : nullptr; D.lo = b->lo; D.up = b->up;
-    D.l = pl.n_bounds ? b->l : nullptr; D.u = pl.n_bounds ? b->u : nullptr;
-    D.dq = b->dq; D.x_levels = b->x_levels; D.status = b->status; D.iterations = b->iterations;
-    if (pl.has_regularisation && !b->b_reg) return fail(OSOT_ERR_INVALID, "plan has a regularisation task but b_reg is null");
-    D.b_reg = pl.has_regularisation ? b->b_reg : nullptr;
-    if (pl.has_regularisation && pl.regularisation_dense) {
-        if (!b->A_reg) return fail(OSOT_ERR_INVALID, "the regularisation task has a stored Jacobian but A_reg is null");
-        D.A_reg = b->A_reg;
-    }
+    const char* why = "";
+    const int rc = fill_batch_ptrs(pl, P, *b, D, &why);
+    if (rc != OSOT_OK) return fail(rc, why);
     D.prof = prof;
-    D.accepted_slack = b->accepted_slack;
     D.hot = (s->hotstart && !prof) ? s->d_hot : nullptr;
     D.rows_scratch = s->d_rows;
     hipStream_t st = (hipStream_t)hip_stream;
@@ -745,13 +711,8 @@ static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
     if (control && control->K_pairs > 0 && (control->Bt.pair_dist || control->Bt.pair_J)) box = false;
     if (control && (prof || !fused))
         return fail(OSOT_ERR_UNSUPPORTED, "the fused control cycle carries no profiling code (use osot_kinematics + osot_cycle)");
-    std::pair<hipEvent_t, hipEvent_t> ev;
-    const bool timed = s->timing && (s->timing_count++ % s->timing_stride) == 0;   // (after EVERY early return: nothing is taken from the pool for a launch that does not happen)
-    if (timed) {
-        if (!s->pool.empty()) { ev = s->pool.back(); s->pool.pop_back(); }
-        else { HIP_TRY(hipEventCreate(&ev.first)); HIP_TRY(hipEventCreate(&ev.second)); }
-        HIP_TRY(hipEventRecord(ev.first, st));
-    }
+    TimedLaunch tl;   // (after EVERY early return: nothing is taken from the pool for a launch that does not happen)
+    if (int r = timed_begin(s, st, tl)) return r;
     const bool roll = control && (control->steps > 1 || control->dq_steps || control->status_steps);
     by_np(T, [&](auto np) {
         constexpr int NP = decltype(np)::value;
@@ -807,10 +768,7 @@ static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
         return 0;
     });
     HIP_TRY(hipGetLastError());
-    if (timed) {
-        HIP_TRY(hipEventRecord(ev.second, st));
-        s->events.push_back(ev);
-    }
+    if (int r = timed_end(s, st, tl)) return r;
     if (s->schedule == 1) {   // this launch's order workgroup has written the order for the next solve of a batch of this size
         s->flip ^= 1;
         s->order_B = b->B;
@@ -890,12 +848,7 @@ static int qp_solve_batch_impl(int B, int n, int nc, const double* H, const doub
     Q.eps_abs = eps_abs;
     Q.H = H; Q.g = g; Q.A = A; Q.lA = lA; Q.uA = uA; Q.l = l; Q.u = u;
     Q.x = x; Q.status = status; Q.iterations = iterations;
-    // the lane layout of the cascade kernels (make_dev_plan): 32, 40 (33..38 variables, two wavefronts per SIMD), 56, 64
-#ifdef OSOT_X_NO_NP40
-    const int T = n <= 32 ? 32 : 64;
-#else
-    const int T = n <= 32 ? 32 : (n <= WaveCtx<40>::NMAX ? 40 : (n <= WaveCtx<56>::NMAX ? 56 : 64));
-#endif
+    const int T = pick_np(n);   // the lane layout of the cascade kernels
     const size_t lds = (size_t)lds_layout(T, nc, &Q.lds_rows_off, &Q.lds_rows_cap) * sizeof(double);
     Q.hot = hot;
     const unsigned grid = (unsigned)B;

@@ -31,20 +31,6 @@ struct TeamTurns {
     Turns* T;
     void sync() const { T->pass(); T->wait_turn(tid); }
 };
-
-void fill_batch(const osot_plan_desc& pd, const osot_qp_batch& qb, osot::wide::Batch& D) {
-    std::memset(&D, 0, sizeof(D));
-    D.B = qb.B;
-    for (int k = 0; k < pd.n_levels; ++k) {
-        D.A[k] = qb.A[k]; D.b[k] = qb.b[k]; D.w[k] = qb.w[k]; D.c[k] = qb.c[k]; D.WA[k] = qb.WA[k]; D.Wb[k] = qb.Wb[k];
-    }
-    D.C = qb.C; D.lo = qb.lo; D.up = qb.up;
-    D.l = pd.n_bounds ? qb.l : nullptr; D.u = pd.n_bounds ? qb.u : nullptr;
-    D.b_reg = pd.has_regularisation ? qb.b_reg : nullptr;
-    D.A_reg = (pd.has_regularisation && pd.regularisation_dense) ? qb.A_reg : nullptr;
-    D.dq = qb.dq; D.x_levels = qb.x_levels; D.accepted_slack = qb.accepted_slack;
-    D.status = qb.status; D.iterations = qb.iterations;
-}
 }  // namespace
 
 // qb: host pointers, as osot_ihqp_solve takes device pointers.  task_active: [OSOT_MAX_LEVELS * OSOT_MAX_TASKS] or null.
@@ -56,7 +42,10 @@ int wide_host_ihqp(const osot_plan_desc* pd, const osot_qp_batch* qb, const unsi
     wide::Plan P;
     wide::make_plan(*pd, qb->level_active, task_active, P);
     wide::Batch D;
-    fill_batch(*pd, *qb, D);
+    std::memset(&D, 0, sizeof(D));
+    const char* why = "";
+    const int rc = fill_batch_ptrs(*pd, P, *qb, D, &why);   // (the product's checks and null-out rules: wide_launch)
+    if (rc != OSOT_OK) return rc;
     const int n = P.n;
     std::vector<double> slot(2 * (size_t)n * n);
     std::vector<double> smem((wide::shared_bytes(n, P.nrows) + 7) / 8 + 2);

@@ -25,14 +25,8 @@ extern "C" __attribute__((visibility("default"))) int emu_ihqp_solve(const osot_
     make_dev_plan(*plan, b->level_active, P, T, lds, task_active);
     DevBatch D;
     memset(&D, 0, sizeof(D));
-    D.B = b->B;
-    for (int k = 0; k < plan->n_levels; ++k) { D.A[k] = b->A[k]; D.b[k] = b->b[k]; D.w[k] = b->w[k]; D.c[k] = b->c[k];
-                                               D.WA[k] = b->WA[k]; D.Wb[k] = b->Wb[k]; }
-    D.C = b->C; D.lo = b->lo; D.up = b->up; D.l = b->l; D.u = b->u;
-    D.dq = b->dq; D.x_levels = b->x_levels; D.status = b->status; D.iterations = b->iterations;
-    D.b_reg = plan->has_regularisation ? b->b_reg : nullptr;
-    D.A_reg = (plan->has_regularisation && plan->regularisation_dense) ? b->A_reg : nullptr;
-    D.accepted_slack = b->accepted_slack;
+    rc = fill_batch_ptrs(*plan, P, *b, D, &why);   // (the product's checks and null-out rules: ihqp_launch)
+    if (rc != OSOT_OK) { fprintf(stderr, "emu: %s\n", why); return rc; }
     D.hot = hot;
     std::vector<double> rows_scratch(P.rows_in_global ? (size_t)b->B * P.rows_doubles : 1);
     D.rows_scratch = rows_scratch.data();
@@ -66,7 +60,7 @@ extern "C" __attribute__((visibility("default"))) int emu_qp_solve_batch(int B, 
     Q.max_iter = max_iter > 0 ? max_iter : 20 * (n + nc) + 100;
     Q.eps_abs = eps_abs;
     Q.H = H; Q.g = g; Q.A = A; Q.lA = lA; Q.uA = uA; Q.l = l; Q.u = u; Q.x = x; Q.status = status; Q.iterations = iterations;
-    const int T = n <= 32 ? 32 : (n <= WaveCtx<40>::NMAX ? 40 : (n <= WaveCtx<56>::NMAX ? 56 : 64));   // as qp_solve_batch_impl
+    const int T = pick_np(n);   // as qp_solve_batch_impl
     const size_t lds = (size_t)lds_layout(T, nc, &Q.lds_rows_off, &Q.lds_rows_cap) * sizeof(double);
     const unsigned grid = (unsigned)B;
     if (T == 32) emu::launch(osot_qp_kernel<32>, grid, lds, 64, Q);

@@ -56,10 +56,19 @@ def emu_lib():
     return _emu
 
 
-def emu_cascade(plan, asm, active=None, task_active=None, hot=None):
+def null_batch_pointer(qb, name, level=None):
+    """a batch as a caller that forgot one array hands it over: qb.name, or qb.name[level], becomes null"""
+    if level is None:
+        setattr(qb, name, None)
+    else:
+        getattr(qb, name)[level] = None
+
+
+def emu_cascade(plan, asm, active=None, task_active=None, hot=None, drop=None):
     """run the cascade kernel body on host pointers through the emulator.  task_active: {(level, task): bool}
     (Task::setActive); asm may carry "WA" / "Wb" (levels with a non-diagonal weight, see emu_update); hot: int32
-    [B][L][32 or 64] hot-start state (read and rewritten in place; start from -1 everywhere), None = cold start"""
+    [B][L][32 or 64] hot-start state (read and rewritten in place; start from -1 everywhere), None = cold start.
+    drop: (name, level or None) of a batch pointer to hand over as null -- the return code alone comes back"""
     B, n, L = asm["B"], asm["n"], asm["L"]
     qb = abi.QpBatch()
     qb.B = B
@@ -110,8 +119,12 @@ def emu_cascade(plan, asm, active=None, task_active=None, hot=None):
             ta[k * abi.MAX_TASKS + j] = 1 if on else 0
     if hot is not None:
         assert hot.dtype == np.int32 and hot.flags.c_contiguous and hot.shape == (B, L, 32 if n <= 32 else 64)
+    if drop is not None:
+        null_batch_pointer(qb, *drop)
     rc = emu_lib().emu_ihqp_solve(C.byref(pd), C.byref(qb), C.cast(ta, C.c_void_p) if ta is not None else None,
                                   hot.ctypes.data if hot is not None else None)
+    if drop is not None:
+        return rc
     assert rc in (0, 100)        # (100: the BOX instantiation ran -- OSOT_EMU_BOX=1, see tests/emu/emu_driver.cpp)
     emu_cascade.ran_box = (rc == 100)
     return dq, xl, st, it

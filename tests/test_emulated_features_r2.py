@@ -2,6 +2,7 @@
 hardware only), body-frame Cartesian tasks, per-row TaskToConstraint bands, collision rows chosen among more candidates
 than rows, non-diagonal weight matrices, Task::setActive, more than four row blocks, the inverse-dynamics producers and
 computedTorque.  tests/test_gpu_features_r2.py repeats them through the C-ABI on hardware."""
+import copy
 import ctypes as C
 
 import numpy as np
@@ -58,11 +59,15 @@ def test_feature_stack_update_and_cascade(n, oracle):
         rq = oracle.ihqp_solve_batch(asm, oracle.BE_QPOASES_REF, nthreads=1, termination_tolerance=10 * 2.221e-16)
         ok = rq["status"] == 1      # (run to the exact optimum qpOASES itself gives up on some instances)
         assert ok.mean() > 0.5 and np.abs(dq[ok] - rq["dq"][ok]).max() < 1e-7
-    # the full W matters: with its diagonal only the answer is a different one
+    # the full W matters: with its diagonal only the answer is a different one (the plan says so too: a level with a dense weight
+    # and no WA / Wb is refused, as by osot_ihqp_solve)
     asm_d = dict(asm); asm_d["Wdense"] = [None] * 3; asm_d.pop("WA"); asm_d.pop("Wb")
     asm_d["w"] = [w.copy() for w in asm["w"]]
     asm_d["w"][1][:, :6] = np.einsum("bii->bi", W)[:, :6]
-    assert np.abs(emu_cascade(plan, asm_d)[0] - dq).max() > 1e-6
+    plan_d = copy.deepcopy(plan)
+    for t in plan_d.levels[1]:
+        t.dense_weight = False
+    assert np.abs(emu_cascade(plan_d, asm_d)[0] - dq).max() > 1e-6
 
 
 @pytest.mark.parametrize("off", [[(1, 0)], [(1, 1), (1, 2)], [(2, 0)], [(0, 0)]])

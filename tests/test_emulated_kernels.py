@@ -652,3 +652,18 @@ def test_indefinite_hessian_is_reported_not_solved(n):
     assert np.abs(x[1]).max() == 0.0 and np.abs(x[3]).max() == 0.0
     for i in (0, 2):
         assert np.abs(x[i] + np.linalg.solve(H[i] + 1e-9 * np.eye(n), g[i])).max() < 1e-9
+
+
+@pytest.mark.parametrize("drop", [("b", 1), ("A", 0), ("lo", None), ("up", None), ("l", None), ("u", None), ("dq", None), ("b_reg", None)],
+                         ids=lambda d: d[0] if d[1] is None else f"{d[0]}{d[1]}")
+def test_missing_batch_pointer_is_refused(drop, oracle):
+    """the emulator runs the batch check of osot_ihqp_solve (fill_batch_ptrs, osot_plan_shape.h): a null b[k], a null A[k] on a
+    level with stored rows, lo/up missing with constraint rows, l/u missing with bounds, a null dq, b_reg missing with a
+    regularisation task are OSOT_ERR_INVALID -- not a fault of the process"""
+    from opensot_amd import abi
+    plan, leaf = synth.make_generic_stack(2, 40, [10, 12], n_eq=2, n_ineq=3, seed=5)
+    synth.add_regularisation(plan, leaf, kind=abi.TASK_GENERIC, rows=None, weight=1e-2, seed=3)
+    assert plan.nc > 0 and plan.bounds and plan.ma(0) > 0 and plan.regularisation is not None
+    asm = oracle.assemble(plan, leaf)
+    assert emu_cascade(plan, asm, drop=drop) == abi.ERR_INVALID
+    assert (emu_cascade(plan, asm)[2] == 0).all()      # (the complete batch is solved)

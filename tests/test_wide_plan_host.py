@@ -10,6 +10,7 @@ import pytest
 
 from opensot_amd import abi, synth
 from opensot_amd.solver import stored_rows
+from helpers import null_batch_pointer
 from oracle import pyoracle
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -20,7 +21,7 @@ def wide_lib():
     global _wide
     if _wide is None:
         so = os.path.join(ROOT, "tests", "emu", "libosot_wide_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_cascade_wide.h", "osot_qp_big.h")] + \
+        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_cascade_wide.h", "osot_qp_big.h", "osot_plan_shape.h")] + \
                [os.path.join(ROOT, "tests", "emu", "cascade_wide_host.cpp")]
         if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
             subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build_wide.sh")])
@@ -29,8 +30,9 @@ def wide_lib():
     return _wide
 
 
-def wide_host(plan, asm, active=None, task_active=None, nthreads=1, t0_last=False):
-    """the wide cascade on host arrays (asm: oracle layout) -> dq, x_levels, status, iterations, accepted_slack"""
+def wide_host(plan, asm, active=None, task_active=None, nthreads=1, t0_last=False, drop=None):
+    """the wide cascade on host arrays (asm: oracle layout) -> dq, x_levels, status, iterations, accepted_slack
+    drop: (name, level or None) of a batch pointer to hand over as null -- the return code alone comes back"""
     B, n, L = asm["B"], asm["n"], asm["L"]
     qb = abi.QpBatch()
     qb.B = B
@@ -69,8 +71,12 @@ def wide_host(plan, asm, active=None, task_active=None, nthreads=1, t0_last=Fals
         for (k, j), on in task_active.items():
             ta[k * abi.MAX_TASKS + j] = 1 if on else 0
     pd = plan.to_c()
+    if drop is not None:
+        null_batch_pointer(qb, *drop)
     rc = wide_lib().wide_host_ihqp(C.byref(pd), C.byref(qb), C.cast(ta, C.c_void_p) if ta is not None else None,
                                    nthreads, 1 if t0_last else 0)
+    if drop is not None:
+        return rc
     assert rc == 0
     return dq, xl, st, it, slack
 
@@ -88,6 +94,22 @@ def oracle_solve(asm, active=None):
 
 def close(a, b, tol=1e-8):
     return np.abs(a - b).max() <= tol * max(1.0, np.abs(b).max())
+
+
+# ---- the batch check of osot_ihqp_solve (fill_batch_ptrs, osot_plan_shape.h) is the one the host build runs -----------------------
+MISSING_POINTERS = [("b", 1), ("A", 0), ("lo", None), ("up", None), ("l", None), ("u", None), ("dq", None), ("b_reg", None)]
+
+
+@pytest.mark.parametrize("drop", MISSING_POINTERS, ids=lambda d: d[0] if d[1] is None else f"{d[0]}{d[1]}")
+def test_missing_batch_pointer_is_refused(drop):
+    """a null b[k], a null A[k] on a level with stored rows, lo/up missing with constraint rows, l/u missing with bounds, a null dq,
+    b_reg missing with a regularisation task: OSOT_ERR_INVALID, as from osot_ihqp_solve on a wide handle -- not a fault of the process"""
+    plan, leaf = generic_wide(2, 70, seed=3)
+    synth.add_regularisation(plan, leaf, kind=abi.TASK_GENERIC, rows=None, weight=1e-2, seed=3)
+    assert plan.nc > 0 and plan.bounds and plan.ma(0) > 0 and plan.regularisation is not None
+    asm = pyoracle.assemble(plan, leaf)
+    assert wide_host(plan, asm, drop=drop) == abi.ERR_INVALID
+    assert (wide_host(plan, asm)[2] == 0).all()      # (the complete batch is solved)
 
 
 # ---- validator of the workgroup route ------------------------------------------------------------------------------------------
