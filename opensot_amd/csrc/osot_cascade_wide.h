@@ -136,8 +136,8 @@ OSOT_BIG_FN void cascade_instance(const Team& tm, const Plan& P, const Batch& D,
     }
     OSOT_BIG_FOR(i, n) {
         xprev[i] = 0.0;
-        lb[i] = D.l ? D.l[inst * n + i] : -big::kInf;
-        ub[i] = D.u ? D.u[inst * n + i] : big::kInf;
+        lb[i] = D.l ? D.l[inst * n + i] : -kInfty;
+        ub[i] = D.u ? D.u[inst * n + i] : kInfty;
     }
     if (t0) *slack = 0.0;
     tm.sync();
@@ -151,7 +151,7 @@ OSOT_BIG_FN void cascade_instance(const Team& tm, const Plan& P, const Batch& D,
             if (k + 1 < P.L) {
                 OSOT_BIG_FOR(q, P.m[k]) {
                     const int r = P.nc + P.optoff[k] + q;
-                    rlo[r] = -big::kInf; rup[r] = big::kInf; rptr[r] = unit_code(0); ropt[r] = 0;
+                    rlo[r] = -kInfty; rup[r] = kInfty; rptr[r] = unit_code(0); ropt[r] = 0;
                 }
                 tm.sync();
             }
@@ -163,8 +163,8 @@ OSOT_BIG_FN void cascade_instance(const Team& tm, const Plan& P, const Batch& D,
             const bool on = P.blk_level[j] - 1 == k;
             OSOT_BIG_FOR(q, P.blk_rows[j]) {
                 const int r = P.blk_off[j] + q;
-                rlo[r] = on ? big::clamp_inf(D.lo[inst * P.nc + r]) : -big::kInf;
-                rup[r] = on ? big::clamp_inf(D.up[inst * P.nc + r]) : big::kInf;
+                rlo[r] = on ? big::clamp_inf(D.lo[inst * P.nc + r]) : -kInfty;
+                rup[r] = on ? big::clamp_inf(D.up[inst * P.nc + r]) : kInfty;
             }
         }
         const int m = P.m[k], ma = P.ma[k], npost = m - ma;
@@ -256,8 +256,8 @@ OSOT_BIG_FN void cascade_instance(const Team& tm, const Plan& P, const Batch& D,
             OSOT_BIG_FOR(q, m) {
                 const int r = P.nc + P.optoff[k] + q;
                 const bool void_row = row_off(q);            // inactive task: 0 x = 0 (Task.h:383-387), i.e. no row
-                rlo[r] = void_row ? -big::kInf : 0.0;
-                rup[r] = void_row ? big::kInf : 0.0;
+                rlo[r] = void_row ? -kInfty : 0.0;
+                rup[r] = void_row ? kInfty : 0.0;
                 ropt[r] = void_row ? 0 : 1;
                 rptr[r] = void_row ? unit_code(0)
                         : (q < ma) ? reinterpret_cast<unsigned long long>(Ak + (size_t)q * n) : unit_code(q - ma);   // Postural: e_(q-ma)

@@ -10,11 +10,7 @@ namespace osot {
 // wavefronts per SIMD); 56: the 64-lane solver with the LDS of n <= 54, four wavefronts per CU instead of three (osot_qp_core.h,
 // WaveCtx); 64
 inline int pick_np(int n) {
-#ifdef OSOT_X_NO_NP40   // developer knob (A/B builds)
-    return (n <= 32) ? 32 : ((n <= WaveCtx<56>::NMAX) ? 56 : 64);
-#else
     return (n <= 32) ? 32 : ((n <= WaveCtx<40>::NMAX) ? 40 : ((n <= WaveCtx<56>::NMAX) ? 56 : 64));
-#endif
 }
 // doubles of M1, M2, V of one wave's LDS slice (sizes fixed by NP)
 inline int wave_lds_doubles(int NP) {

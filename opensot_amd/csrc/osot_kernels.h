@@ -113,7 +113,6 @@ static_assert(std::is_trivially_copyable<DevPlan>::value && std::is_trivially_co
 template <int NP, bool PROF, bool EXTRA, bool BOX = false>
 __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D, const long long inst, const int lane, char* osot_smem) {
     constexpr int HV = WaveCtx<NP>::HV, S = WaveCtx<NP>::S;
-    constexpr int HB = (NP % 16 == 0) ? 16 : 8;   // rows of H per broadcast group of the register H build
     const int n = P.n;
     double* base = reinterpret_cast<double*>(osot_smem);
     WaveCtx<NP> w;
@@ -231,17 +230,15 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
         // (defined on EVERY path through the level: left undefined on the diagonal / low-rank paths, the compiler resolves the merge by
         //  keeping the PREVIOUS level's tiles alive across the whole loop body -- 2 x NP / HV registers through the active-set loops,
         //  spilled and reloaded at the loop's back edge in the 64-lane layouts)
-#ifndef OSOT_X_HACC_UNDEF
 #pragma unroll
         for (int ii = 0; ii < NP / HV; ++ii) hacc[ii] = 0.0;
-#endif
         // round 6, 40-lane layout: a dense level (diagonal weights, every task active) under >= 8 equality rows that the previous level's
         // solution satisfies -- the reference's COMAN stacks below their first level -- takes the null-space method AHEAD of the H build:
         // no H, no 40-column factorisation, no row-by-row reflections (nullspace_dense_wide).  -1: not taken (or handed back: rank-deficient
         // rows, more than 24 free columns), the level runs as before.
         int dn_rank = -1, dn_neq = 0;
         double dn_x = 0.0, dn_hinv = 0.0;
-        if constexpr (NP == 40 && kDenseNull40) {
+        if constexpr (NP == 40) {
             if (!diag_h && ma <= kDenseNullRows && !dense && !inact && !regd) {
                 const int nrows_k = P.nc + P.optoff[k];
                 int ne = 0;
@@ -274,15 +271,11 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
         const bool dense_done = dn_rank >= 0;
         bool lowrank = false;   // few stored rows: J and x in closed form, no H, no factorisation (lowrank_prepare32)
         double xprep = 0.0;
-        if constexpr (NP == 32 || (NP == 40 && kLowRank40)) {
-#ifndef OSOT_X_NO_LOWRANK
+        if constexpr (NP == 32 || NP == 40) {
             // (five or six stored rows -- one Cartesian task -- only next to a Postural block over every variable, BASELINE config 2: D >= w
             //  there.  With D = eps alone the scaled rows carry 1 / sqrt(eps) and six of them lose what the Cholesky path keeps: at the
             //  default eps the closed-loop instance of default_eps_stuck_instances[tasks] ended lexicographically worse than eiQuadProg)
             if (!dense_done && !diag_h && (ma <= 4 || (ma <= kLowRankMax && m - ma >= n)) && !dense && !inact && !regd) {
-#else
-            if (false) {
-#endif
                 lowrank = true;
                 const int npost = m - ma;
                 const bool postc = valid && c < npost;
@@ -394,7 +387,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
             g = valid ? ((tq & 1) ? gp1 : gp0) : 0.0;
             const int npost = m - ma;   // Postural block appended to the level: A = [I 0] (Postural.cpp:37)
             if (npost > 0 && c < npost) g -= wrow(ma + c) * bk[ma + c];
-            // diagonal: Postural weights, eps I, unit diagonal beyond n (see factor_rows64 for the padding)
+            // diagonal: Postural weights, eps I, unit diagonal beyond n (the padding factorises to the identity)
 #pragma unroll
             for (int I = 0; I < 2; ++I) {
                 const int i = 16 * I + ta;    // diagonal element (i, i) lives in tile (I, I) where a == q + 4 r
@@ -412,11 +405,11 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
                 for (int C2 = 0; C2 < 2; ++C2)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) hacc[4 * (2 * I + C2) + r] = Ht[I][C2][r];
-          } else if constexpr (kWideTiles) {
+          } else {
             // ---- round 5: the same H build on the matrix core for the 64-lane layouts (33 .. 64 variables): T x T tiles of
             // 16 x 16, the UPPER triangle only (H is symmetric and factor_tiles_wide reads nothing else).  Lane (a, q) of the
             // PHYSICAL lane loads A[r0 + q][16 X + a], X < T: T coalesced loads cover four rows, and those registers are the
-            // MFMA operands of every tile -- where the register build below spends an LDS broadcast and NP fma per row and lane.
+            // MFMA operands of every tile -- where the register build it replaced (in the history) spent an LDS broadcast and NP fma per row and lane.
             constexpr int T = wide_tiles(NP), NT = (T * (T + 1)) / 2;
             const int ta = lane & 15, tq = lane >> 4;
             v4f64 Ht[NT];
@@ -529,91 +522,6 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
             for (int t = 0; t < NT; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) hacc[4 * t + r] = Ht[t][r];
-          } else {
-            // ---- H = A'WA + eps I, g = -A'Wb + c.  Lane (c,h) accumulates H[i][c] for i = ii*HV + h in
-            // registers; stored rows are staged four at a time through LDS for the broadcasts.
-#pragma unroll
-            for (int ii = 0; ii < NP / HV; ++ii) hacc[ii] = 0.0;
-            for (int r0 = 0; r0 < ma; r0 += 4) {
-                OSOT_SUB_BEGIN();
-                double a[4], wa[4];
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const int r = r0 + u;
-                    const bool in = r < ma && !(inact && row_off(r));
-                    a[u] = (in && valid) ? Ak[r * n + c] : 0.0;
-                    if (dense) wa[u] = (in && valid) ? WAk[r * n + c] : 0.0;
-                    else wa[u] = (in ? (wk ? wk[r] : 1.0) : 0.0) * a[u];
-                    g -= dense ? a[u] * (in ? Wbk[r] : 0.0) : wa[u] * (in ? bk[r] : 0.0);
-                }
-                wave_sync();   // the previous group's broadcasts are done
-                OSOT_SUB_END(PH_INV);     // (profiling slot reused: wait for the rows)
-                if (h == 0) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) w.V[u * WaveCtx<NP>::LW + c] = a[u];
-                }
-                wave_sync();
-#pragma unroll
-                for (int u = 0; u < 4; ++u) {
-                    const double* Vu = w.V + u * WaveCtx<NP>::LW + h;
-#pragma unroll
-                    for (int i0 = 0; i0 < NP / HV; i0 += HB) {
-                        double vv[HB];
-#pragma unroll
-                        for (int t = 0; t < HB; ++t) vv[t] = Vu[(i0 + t) * HV];
-#pragma unroll
-                        for (int t = 0; t < HB; ++t) hacc[i0 + t] = fma(wa[u], vv[t], hacc[i0 + t]);
-                    }
-                }
-                OSOT_SUB_END(PH_SUBST);   // (profiling slot reused: LDS broadcast + outer product)
-            }
-            if (regd) {   // the regularisation task's stored rows (see the NP = 32 branch)
-                const double* Ar = D.A_reg + inst * (long long)P.reg_rows * n;
-                const double* br = D.b_reg + inst * P.reg_rows;
-                for (int r0 = 0; r0 < P.reg_rows; r0 += 4) {
-                    double a[4], wa[4];
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const int r = r0 + u;
-                        const bool in = r < P.reg_rows;
-                        a[u] = (in && valid) ? Ar[r * n + c] : 0.0;
-                        wa[u] = P.reg_w * a[u];
-                        g -= wa[u] * (in ? br[r] : 0.0);
-                    }
-                    wave_sync();
-                    if (h == 0) {
-#pragma unroll
-                        for (int u = 0; u < 4; ++u) w.V[u * WaveCtx<NP>::LW + c] = a[u];
-                    }
-                    wave_sync();
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) {
-                        const double* Vu = w.V + u * WaveCtx<NP>::LW + h;
-#pragma unroll
-                        for (int i0 = 0; i0 < NP / HV; i0 += HB) {
-                            double vv[HB];
-#pragma unroll
-                            for (int t = 0; t < HB; ++t) vv[t] = Vu[(i0 + t) * HV];
-#pragma unroll
-                            for (int t = 0; t < HB; ++t) hacc[i0 + t] = fma(wa[u], vv[t], hacc[i0 + t]);
-                        }
-                    }
-                }
-            }
-            if (m > ma && c < m - ma) {   // Postural block appended to the level: A = [I 0] (Postural.cpp:37)
-                const double wi = wrow(ma + c);
-                g -= wi * bk[ma + c];
-#pragma unroll
-                for (int ii = 0; ii < NP / HV; ++ii) if (ii * HV + h == c) hacc[ii] += wi;
-            }
-            wave_sync();
-#pragma unroll
-            for (int ii = 0; ii < NP / HV; ++ii) {
-                const int i = ii * HV + h;
-                // factorised straight from these registers; unit diagonal beyond n (see factor_rows64)
-                hacc[ii] += (i == c) ? (valid ? P.eps_abs + dreg : 1.0) : 0.0;
-            }
-            wave_sync();
           }
         } else if (valid) {   // level = one Postural block [I_m 0]: H = blockdiag(W, 0) + eps I is diagonal
             const bool inb = c < m;
@@ -826,7 +734,7 @@ __global__ void __launch_bounds__(64, (NP == 40 ? OSOT_WAVES40 : 1)) osot_qp_ker
             Hc[t] = (i < n && cc < n) ? Q.H[(inst * n + i) * n + cc] + ((i == cc) ? Q.eps_abs : 0.0)
                                       : ((i == cc) ? 1.0 : 0.0);   // unit diagonal beyond n
         }
-    } else if constexpr (kWideTiles) {   // the upper triangle of 16 x 16 tiles (factor_tiles_wide): Hc[4 tile_u(I, C) + r] = H[16 I + q + 4 r][16 C + a]
+    } else {   // the upper triangle of 16 x 16 tiles (factor_tiles_wide): Hc[4 tile_u(I, C) + r] = H[16 I + q + 4 r][16 C + a]
         constexpr int T = wide_tiles(NP);
         const int ta = lane & 15, tq = lane >> 4;
 #pragma unroll
@@ -839,13 +747,6 @@ __global__ void __launch_bounds__(64, (NP == 40 ? OSOT_WAVES40 : 1)) osot_qp_ker
                     Hc[4 * tile_u<T>(I, C2) + r] = (i < n && cc < n) ? Q.H[(inst * n + i) * n + cc] + ((i == cc) ? Q.eps_abs : 0.0)
                                                                       : ((i == cc) ? 1.0 : 0.0);   // unit diagonal beyond n
                 }
-    } else {
-#pragma unroll
-        for (int ii = 0; ii < NP / HV; ++ii) {
-            const int i = HV * ii + h;
-            Hc[ii] = (valid && i < n) ? Q.H[(inst * n + i) * n + c] + ((i == c) ? Q.eps_abs : 0.0)
-                                      : ((i == c) ? 1.0 : 0.0);   // unit diagonal beyond n (see factor_rows64)
-        }
     }
     wave_sync();
     const double g = valid ? Q.g[inst * n + c] : 0.0;

@@ -49,6 +49,8 @@ struct DevNhqp {
 };
 
 constexpr int kNS = 33;              // LDS row stride of the 32-column work matrices
+constexpr double kEps = 2.220446049250313e-16;   // fp64 unit round-off: the QL iterations' deflation test
+constexpr double kSvNoise = 1.0e-7;  // a singular value below this fraction of the largest is noise of the Gram matrix, not a direction
 #ifndef OSOT_QL_TOL
 #define OSOT_QL_TOL 1.0
 #endif
@@ -84,10 +86,7 @@ __device__ __forceinline__ double dot_half(const double* a, int sa, const double
 //  -- loop counters in VGPRs, exec-mask branches, a null check in front of every access through the generic pointers)
 // phase 1 + 2 of sym_eig32: K (k x k symmetric) -> tridiagonal (d, e: one entry per lane, e[c] coupling c - 1 and c as tred2 leaves
 // it) and K <- the accumulated orthogonal transformation Q (A = Q T Q')
-// ACCUM = false: the tridiagonal form only (d, e), K is left in pieces -- for callers that want eigenVALUES alone
-template <bool ACCUM = true>
 __device__ __forceinline__ void sym_tred2_32(double* K, double* E, int k, int c, int h, double& d_out, double& e_out) {
-    constexpr double kEps = 2.220446049250313e-16;
     double d = 0.0, e = 0.0;                 // lane j: d[j], e[j]
     const bool wr = (h == 0);
     // ---- one exact scaling of the whole matrix (a power of two, largest entry into [0.5, 1)) instead of tred2's scaling of every
@@ -171,11 +170,6 @@ __device__ __forceinline__ void sym_tred2_32(double* K, double* E, int k, int c,
         }
         if (c == i) { e = e_i; d = hv; }
     }
-    if constexpr (!ACCUM) {       // the diagonal of the tridiagonal form sits on K's diagonal (the accumulation below does not move it)
-        const double kcc = K[c * kNS + c];
-        d_out = scale_pow2((c < k) ? kcc : 0.0, kexp); e_out = scale_pow2(e, kexp);
-        return;
-    }
     // ---- accumulate the transformations: K becomes the orthogonal Q
     for (int i = 0; i < k; ++i) {
         const int l = i - 1;
@@ -216,7 +210,8 @@ __device__ __forceinline__ void sym_tred2_32(double* K, double* E, int k, int c,
     d_out = scale_pow2(d, kexp); e_out = scale_pow2(e, kexp);
 }
 
-// Round 6: sym_tred2_32<false> with the matrix in REGISTERS.  The LDS form above pays, per reflector step, two chunked passes over the
+// Round 6: the tridiagonal form ALONE (d, e and the stored reflectors; K is left in pieces, no Q: for callers that want eigenVALUES, or
+// the eigenvectors of a few), with the matrix in REGISTERS.  The LDS form above pays, per reflector step, two chunked passes over the
 // lane's row (8 reads in flight, ~150 clocks per chunk and dependent on the one before) with two synchronisations around them: 4.5 k
 // clocks per step, 100 k of the 270 k clocks of a 24 x 29 level (BASELINE config 3's level 1).  Here lane c keeps row c of the
 // symmetric work matrix in 32 registers (both halves the same row: nothing is split, nothing is exchanged through LDS), the
@@ -230,11 +225,6 @@ template <int P, int N, class F>
 __device__ __forceinline__ void nh_static_for(F& f) {
     if constexpr (P < N) { f(std::integral_constant<int, P>{}); nh_static_for<P + 1, N>(f); }
 }
-#ifndef OSOT_X_TRED2_LDS
-constexpr bool kTred2Regs = true;
-#else
-constexpr bool kTred2Regs = false;      // (A/B builds: the LDS form)
-#endif
 __device__ __forceinline__ void sym_tred2_32_regs(double* K, int k, int c, int h, double& d_out, double& e_out) {
     double e = 0.0;
     const bool wr = (h == 0);
@@ -303,7 +293,6 @@ __device__ __forceinline__ void sym_tred2_32_regs(double* K, int k, int c, int h
 
 // phase 3 of sym_eig32: implicit QL with shifts on (d, e) (lane c: d[c]; e[c] couples c - 1 and c on entry), rotations into the columns of K
 __device__ __forceinline__ void sym_ql_32(double* K, int k, int c, int h, double& d, double& e) {
-    constexpr double kEps = 2.220446049250313e-16;
     // ---- implicit QL with shifts on (d, e); the rotations go into the columns of K (tql2)
     {   // e[j] <- e[j + 1]  (the shuffle OUTSIDE the select: a ds_bpermute under a partial exec mask reads zeros from the
         // lanes that are masked off, and lane k - 2 needs lane k - 1)
@@ -395,7 +384,7 @@ __device__ __forceinline__ void sym_eig_finish_32(double* K, double* E, int k, i
 // make the routine return false BEFORE anything is overwritten, and the caller runs the QL iteration on the same (d, e, Q).
 // d, e as sym_tred2_32 leaves them (e[c] couples c - 1 and c).  On true: K = eigenvectors (columns), d = this lane's eigenvalue.
 // MODE 1: the full decomposition (above).  MODE 0: the eigenvalues alone (d <- eigenvalue number c, ascending; always succeeds:
-// clusters are no obstacle to counting).  MODE 2 (K holds what sym_tred2_32<false> left: the reflectors, not Q): the eigenvalues
+// clusters are no obstacle to counting).  MODE 2 (K holds what sym_tred2_32_regs left: the reflectors, not Q): the eigenvalues
 // and the eigenVECTORS of the nl smallest ones only -- those below thr2 times the largest -- as columns 0 .. nl - 1 of E (twisted
 // factorisation, then back-transformed through the stored reflectors); false if the matrix is rank deficient at noise level or
 // one of those eigenvalues sits in a cluster (the caller then takes the full route).
@@ -568,68 +557,35 @@ __device__ __forceinline__ bool sym_bisect_32(double* K, double* E, int k, int c
         // my column of Y normalised in place, then V = H_(k-1) .. H_2 Y for every column at once (lane = column, its entries split
         // over the halves): tred2 left reflector i as row i of K (u) and column i of K (u / H); what Q would have cost to build
         // and to multiply is k - 2 dot products and updates of a column here.  Only the first nl columns are used afterwards.
-        if constexpr (kTred2Regs) {
-            // (round 6) my column of Y in 32 registers, both halves the same column: the reflector's two vectors are uniform-address LDS
-            // reads in flight together, the dot product is lane-local, no synchronisation between the steps (a column belongs to its lane)
-            double y[32];
+        // (round 6) my column of Y in 32 registers, both halves the same column: the reflector's two vectors are uniform-address LDS
+        // reads in flight together, the dot product is lane-local, no synchronisation between the steps (a column belongs to its lane)
+        double y[32];
 #pragma unroll
-            for (int kk = 0; kk < 32; ++kk) { const double v = E[kk * kNS + c]; y[kk] = (kk < k) ? v * rs : 0.0; }
-            auto bstep = [&](auto ic) {
-                constexpr int I = decltype(ic)::value;       // 2 .. 31
-                constexpr int L = I - 1;
-                if (I >= k) return;                          // (uniform)
-                double u[L + 1], uh[L + 1];
+        for (int kk = 0; kk < 32; ++kk) { const double v = E[kk * kNS + c]; y[kk] = (kk < k) ? v * rs : 0.0; }
+        auto bstep = [&](auto ic) {
+            constexpr int I = decltype(ic)::value;       // 2 .. 31
+            constexpr int L = I - 1;
+            if (I >= k) return;                          // (uniform)
+            double u[L + 1], uh[L + 1];
 #pragma unroll
-                for (int kk = 0; kk <= L; ++kk) { u[kk] = K[I * kNS + kk]; uh[kk] = K[kk * kNS + I]; }
-                double de = 0.0, dq = 0.0;                   // (the two halves' partial sums of the LDS form)
+            for (int kk = 0; kk <= L; ++kk) { u[kk] = K[I * kNS + kk]; uh[kk] = K[kk * kNS + I]; }
+            double de = 0.0, dq = 0.0;                   // (the two halves' partial sums of the LDS form)
 #pragma unroll
-                for (int kk = 0; kk <= L; ++kk) {
-                    if (kk & 1) dq = fma(u[kk], y[kk], dq);
-                    else de = fma(u[kk], y[kk], de);
-                }
-                const double dot = h ? dq + de : de + dq;
-#pragma unroll
-                for (int kk = 0; kk <= L; ++kk) y[kk] = fma(-dot, uh[kk], y[kk]);
-            };
-            nh_static_for<2, 32>(bstep);
-            wave_sync();
-            if (in && h == 0) {
-#pragma unroll
-                for (int kk = 0; kk < 32; ++kk) if (kk < k) E[kk * kNS + c] = y[kk];
+            for (int kk = 0; kk <= L; ++kk) {
+                if (kk & 1) dq = fma(u[kk], y[kk], dq);
+                else de = fma(u[kk], y[kk], de);
             }
-            wave_sync();
-            return true;
-        }
+            const double dot = h ? dq + de : de + dq;
 #pragma unroll
-        for (int t = 0; t < 16; ++t) { const int r = 2 * t + h; const double v = E[r * kNS + c]; if (r < k && in) E[r * kNS + c] = v * rs; }
+            for (int kk = 0; kk <= L; ++kk) y[kk] = fma(-dot, uh[kk], y[kk]);
+        };
+        nh_static_for<2, 32>(bstep);
         wave_sync();
-        for (int i = 2; i < k; ++i) {
-            const int l = i - 1;
-            double dot = 0.0;
-            for (int base = 0; base <= l; base += 8) {
+        if (in && h == 0) {
 #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int kk = base + 2 * t + h;
-                    const double u = K[i * kNS + kk], y = E[kk * kNS + c];
-                    dot = fma((kk <= l) ? u : 0.0, y, dot);
-                }
-            }
-            dot = halfsum<32>(dot);
-            for (int base = 0; base <= l; base += 8) {
-                double nv[4];
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int kk = base + 2 * t + h;
-                    nv[t] = fma(-dot, K[kk * kNS + i], E[kk * kNS + c]);
-                }
-#pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int kk = base + 2 * t + h;
-                    if (kk <= l && in) E[kk * kNS + c] = nv[t];
-                }
-            }
-            wave_sync();
+            for (int kk = 0; kk < 32; ++kk) if (kk < k) E[kk * kNS + c] = y[kk];
         }
+        wave_sync();
         return true;
     }
     // (my column of Y in registers; Q is zero beyond column k and E holds finite numbers there: fixed trip counts, no masks; two rows
@@ -667,12 +623,8 @@ __device__ __forceinline__ void sym_eig32_fast(double* K, double* E, int k_in, i
     if (blockIdx.x == 0 && threadIdx.x == 0) printf("PHASE    tred2 k=%d %lld\n", k, (long long)clock64() - t0_);
     t0_ = (long long)clock64();
 #endif
-#ifndef OSOT_X_NO_BISECT
     // (the bisection has a floor of ~20 k clocks -- 36 sweeps whatever the size -- and QL costs ~470 k^2: they cross near k = 10)
     const bool done = (k >= 10) && uniform_b(sym_bisect_32(K, E, k, c, h, d, e));
-#else
-    const bool done = false;
-#endif
     if (!done) sym_ql_32(K, k, c, h, d, e);
 #ifdef OSOT_NHQP_PHASES
     if (blockIdx.x == 0 && threadIdx.x == 0) printf("PHASE    bisect/ql done=%d %lld\n", (int)done, (long long)clock64() - t0_);
@@ -692,8 +644,7 @@ __device__ __forceinline__ void sym_eig32_fast(double* K, double* E, int k_in, i
 __device__ __forceinline__ bool sym_eig_selected32(double* K, double* E, int k_in, int c, int h, double thr2, double& lam, int& nl) {
     const int k = uniform_i(k_in);
     double d, e;
-    if constexpr (kTred2Regs) sym_tred2_32_regs(K, k, c, h, d, e);
-    else sym_tred2_32<false>(K, E, k, c, h, d, e);
+    sym_tred2_32_regs(K, k, c, h, d, e);
     int nsel = 0;
     const bool ok = uniform_b(sym_bisect_32<2>(K, E, k, c, h, d, e, thr2, &nsel));
     wave_sync();
@@ -705,8 +656,7 @@ __device__ __forceinline__ bool sym_eig_selected32(double* K, double* E, int k_i
 __device__ __forceinline__ double sym_eigvals32(double* K, double* E, int k_in, int c, int h) {
     const int k = uniform_i(k_in);
     double d, e;
-    if constexpr (kTred2Regs) sym_tred2_32_regs(K, k, c, h, d, e);
-    else sym_tred2_32<false>(K, E, k, c, h, d, e);
+    sym_tred2_32_regs(K, k, c, h, d, e);
     sym_bisect_32<0>(K, E, k, c, h, d, e);
     wave_sync();
     if (h == 0) { K[c * kNS + 32] = 0.0; E[c * kNS + 32] = 0.0; }
@@ -1009,7 +959,6 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare_kernel(const DevNhqp Q) 
     // ---- Gram matrix of the small side
     const bool rowside = m <= nf;
     const int k = rowside ? m : nf;
-    constexpr double kSvNoise = 1.0e-7;
     auto build_gram = [&]() {
     if (rowside) {          // K[a][c] = <row a, row c> of AN
         const int cm = (c < m) ? c : 0;
@@ -1257,41 +1206,7 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare_kernel(const DevNhqp Q) 
         gacc = halfsum<32>(gacc);
         if (h == 0 && c < nf) Q.g[inst * nf + c] = gacc;
         const bool sel = ns > 0 && Q.sel_reg;
-#ifndef OSOT_NHQP_H_VALU
         nhqp_gram_to<2>(Hg, nf, nf, AN, kNS, m, vec, V2, kNS, nf, nullptr, sel ? ns : 0, sv_max, lane);     // (round 5: on the matrix core; nf <= 32 here)
-#else
-        double v2c[16];                             // my row of V2 (zero beyond ns)
-#pragma unroll
-        for (int t = 0; t < 16; ++t) { const double v = V2[cc * kNS + 2 * t + h]; v2c[t] = (sel && 2 * t + h < ns) ? sv_max * v : 0.0; }
-        // (two rows of H per trip: their products are independent chains; row nf of an odd count is computed on row nf - 1 again)
-        for (int i0 = 0; i0 < nf; i0 += 2) {
-            const int i1 = (i0 + 1 < nf) ? i0 + 1 : i0;
-            double a0 = 0.0, a1 = 0.0, c0 = 0.0, c1 = 0.0;
-#pragma unroll
-            for (int t = 0; t < MR / 2; t += 2) {
-                a0 = fma(wan[t], AN[(2 * t + h) * kNS + i0], a0);
-                a1 = fma(wan[t + 1], AN[(2 * (t + 1) + h) * kNS + i0], a1);
-                c0 = fma(wan[t], AN[(2 * t + h) * kNS + i1], c0);
-                c1 = fma(wan[t + 1], AN[(2 * (t + 1) + h) * kNS + i1], c1);
-            }
-            if (sel) {
-#pragma unroll
-                for (int t = 0; t < 16; t += 2) {
-                    // (BOTH factors masked beyond ns: V2 shares its buffer with the twisted factorisation's work, whose unused part
-                    //  may hold Inf after a clamped pivot, and 0 * Inf would poison H -- ADVICE r4)
-                    const bool m0 = 2 * t + h < ns, m1 = 2 * (t + 1) + h < ns;
-                    const double f00 = V2[i0 * kNS + 2 * t + h], f01 = V2[i0 * kNS + 2 * (t + 1) + h];
-                    const double f10 = V2[i1 * kNS + 2 * t + h], f11 = V2[i1 * kNS + 2 * (t + 1) + h];
-                    a0 = fma(v2c[t], m0 ? f00 : 0.0, a0);
-                    a1 = fma(v2c[t + 1], m1 ? f01 : 0.0, a1);
-                    c0 = fma(v2c[t], m0 ? f10 : 0.0, c0);
-                    c1 = fma(v2c[t + 1], m1 ? f11 : 0.0, c1);
-                }
-            }
-            const double acc0 = halfsum<32>(a0 + a1), acc1 = halfsum<32>(c0 + c1);
-            if (h == 0 && c < nf) { Hg[i0 * nf + c] = acc0; if (i1 != i0) Hg[i1 * nf + c] = acc1; }
-        }
-#endif
     }
     NHQP_PHASE("Hg");
     if (Q.Wd) { wave_sync(); nhqp_dense_weight_correction(Q, inst, AN, kNS, b0, (h == 0) ? c : -1); }
@@ -1394,12 +1309,8 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare64_kernel(const DevNhqp Q
         for (int u = 0; u < 8; ++u) mq[u] = first ? 0.0 : (q0col ? bcast(acc8[u], 63) : colsum<64>(a8[u] * vec[lane]));
     };
     // (round 5) the same products on the fp64 matrix core, sixteen rows at a time (nhqp_rows16_times_N: the A operand straight from HBM / L2,
-    // M q0 as column nf of the product -- which needs a spare tile column: nf < 64 below the first level; OSOT_NHQP_ROWS8 keeps the staged form)
-#ifndef OSOT_NHQP_ROWS8
+    // M q0 as column nf of the product -- which needs a spare tile column: nf < 64 below the first level, the staged form otherwise)
     const bool use_tiles = first || nf < 64;
-#else
-    const bool use_tiles = false;
-#endif
     const int Tt = uniform_i((nf + (first ? 0 : 1) + 15) >> 4);
     auto rows16_times_N = [&](const double* M, int rows, int I, auto&& sink) {      // sink(row, col, value) for every entry of the 16 x 16 T tiles
         auto run = [&](auto tc) {
@@ -1518,7 +1429,6 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare64_kernel(const DevNhqp Q
     // two rows of the result per trip
     const bool rowside = m <= nf;
     const int k = rowside ? m : nf;
-    constexpr double kSvNoise = 1.0e-7;
     auto build_gram = [&]() {
     if (rowside) {
         const int cm = (c32 < m) ? c32 : 0;
@@ -1807,38 +1717,8 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare64_kernel(const DevNhqp Q
         }
         if (c < nf) Q.g[inst * nf + c] = gacc;
         const bool sel = ns > 0 && Q.sel_reg;
-#ifndef OSOT_NHQP_H_VALU
         // (round 5) on the matrix core: nhqp_tile_gram -- was two rows of H per trip through the vector unit, 36-58 k clocks a level
         nhqp_gram_to(Hg, nf, nf, AN, S, m, vec, V2, v2s, nf, nullptr, sel ? ns : 0, sv_max, lane);
-#else
-        for (int i0 = 0; i0 < nf; i0 += 2) {
-            const int i1 = (i0 + 1 < nf) ? i0 + 1 : i0;
-            double a0 = 0.0, a1 = 0.0;
-            for (int r0 = 0; r0 < m; r0 += 8) {
-#pragma unroll
-                for (int j = 0; j < 8; ++j) {
-                    const int r = r0 + j;
-                    const double wan = vec[r] * AN[r * S + cc];
-                    a0 = fma(wan, AN[r * S + i0], a0);
-                    a1 = fma(wan, AN[r * S + i1], a1);
-                }
-            }
-            if (sel) {
-                for (int t0 = 0; t0 < ns; t0 += 8) {
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int t = t0 + j;
-                        const double v2ct = V2[cc * v2s + t];               // (loaded, then masked: no branch between the reads of a chunk)
-                        const double own = (t < ns) ? sv_max * v2ct : 0.0;
-                        const double f0 = V2[i0 * v2s + t], f1 = V2[i1 * v2s + t];
-                        a0 = fma(own, (t < ns) ? f0 : 0.0, a0);
-                        a1 = fma(own, (t < ns) ? f1 : 0.0, a1);
-                    }
-                }
-            }
-            if (c < nf) { Hg[i0 * nf + c] = a0; if (i1 != i0) Hg[i1 * nf + c] = a1; }
-        }
-#endif
     }
     NHQP_PHASE("Hg");
     if (Q.Wd) { wave_sync(); nhqp_dense_weight_correction(Q, inst, AN, S, b0, c); }
@@ -1863,7 +1743,7 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare64_kernel(const DevNhqp Q
 //   * always the COLUMN-side Gram matrix G = (A N)'(A N) (nf x nf): its eigenvectors are ALL of V, the null space of A N included
 //     (no Householder completion), whatever the rank;
 //   * Householder tridiagonalisation + implicit QL over all 64 lanes (sym_eig_wide) -- until late in round 5 a parallel cyclic Jacobi
-//     iteration (kept under OSOT_NHQP_WIDE_JACOBI): ~280 rounds of 2 x 18 dependent LDS hand-offs, 93 % of a 7.4 ms launch at S1;
+//     iteration (in the history; docs/HISTORY_r1-r5.md has the measurement): ~280 rounds of 2 x 18 dependent LDS hand-offs, 93 % of a 7.4 ms launch at S1;
 //     the Gram matrix, H and the triplets' u = A N v on the fp64 matrix core (nhqp_tile_gram; T = A N V in one go);
 //   * U = A N V Sigma^-1 explicitly for the min(m, nf) triplets (null triplets: completed by Gram-Schmidt of unit vectors), so that
 //     regularize_A_b is the reference's own formula, b0 <- U diag(d) U'b0, A N <- A N + sum (sv' - sv) u v' (nHQP.cpp:236-279).
@@ -1873,10 +1753,9 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare64_kernel(const DevNhqp Q
 // its eigenvector (V: LDS, stride S; both buffers ZERO beyond k up to the next multiple of eight, rows and columns).  Householder tridiagonalisation
 // (one reflector per column, lane = column for the matrix - vector product and the rank-two update, lane = row for V <- V H) and the
 // implicit QL iteration of sym_ql_32 over all 64 lanes: (d, e) one entry per lane read with v_readlane, a lane's own row of V carried
-// through the rotations.  Replaces the cyclic Jacobi iteration (kept under OSOT_NHQP_WIDE_JACOBI for A/B), which moved ~12 LDS words
+// through the rotations.  Replaces the cyclic Jacobi iteration (in the history), which moved ~12 LDS words
 // per pair per round, ~280 rounds, and was 93 % of the launch.  vv / ww: 64 doubles of LDS scratch each.
 __device__ __forceinline__ bool sym_eig_wide(double* G, double* V, double* vv, double* ww, int k_in, int S_in, int lane) {
-    constexpr double kEps = 2.220446049250313e-16;
     const int k = uniform_i(k_in), S = uniform_i(S_in);
     const int cl = (lane < k) ? lane : 0;
     // ---- V = I
@@ -2114,72 +1993,8 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare_wide_kernel(const DevNhq
     if (lane < nf) NV[lane * S + lane] = 1.0;
     wave_sync();
     NHQP_PHASE("w:gram");
-#ifndef OSOT_NHQP_WIDE_JACOBI
     // ---- eigen-decomposition of G: tridiagonalisation + implicit QL (sym_eig_wide); eigenvalues to the diagonal, V in NV
     const bool eig_ok = sym_eig_wide(G, NV, vec, ub, nf, S, lane);
-#else
-    const bool eig_ok = true;
-    // ---- cyclic Jacobi on G, rotations accumulated in V.  kk = nf rounded up to even (a phantom index pairs with nobody); round r of
-    // a sweep: (kk - 1, r) and ((r + t) mod (kk - 1), (r - t) mod (kk - 1)), t = 1 .. kk / 2 - 1 -- every pair once per sweep.
-    {
-        const int kk = (nf + 1) & ~1, half = kk >> 1, md = kk - 1;
-        double tr = 0.0;
-        if (lane < nf) tr = G[lane * S + lane];
-        const double scale = uniform_d(colsum<64>(fabs(tr)));            // trace: the eigenvalues' scale
-        for (int sweep = 0; sweep < 14; ++sweep) {
-            double off = 0.0;
-            if (lane < nf) for (int a = 0; a < nf; ++a) if (a != lane) { const double v = G[a * S + lane]; off = fma(v, v, off); }
-            off = uniform_d(colsum<64>(off));
-            if (!(off > 1.0e-30 * scale * scale)) break;
-            for (int r = 0; r < md; ++r) {
-                if (lane < half) {
-                    int p, q;
-                    if (lane == 0) { p = md; q = r; }
-                    else { p = (r + lane) % md; q = (r - lane + md) % md; }
-                    if (p > q) { const int t = p; p = q; q = t; }
-                    double cs = 1.0, sn = 0.0;
-                    if (q < nf) {
-                        const double gpq = G[p * S + q], gpp = G[p * S + p], gqq = G[q * S + q];
-                        if (fabs(gpq) > 1.0e-300 && fabs(gpq) > 1.0e-17 * sqrt(fabs(gpp * gqq))) {
-                            const double tau = (gqq - gpp) / (2.0 * gpq);
-                            const double t = ((tau >= 0.0) ? 1.0 : -1.0) / (fabs(tau) + sqrt(1.0 + tau * tau));
-                            cs = 1.0 / sqrt(1.0 + t * t); sn = t * cs;
-                        }
-                    }
-                    pp[lane] = p; pq[lane] = (q < nf) ? q : p; rc[lane] = cs; rs[lane] = sn;     // (phantom partner: identity on p alone)
-                }
-                wave_sync();
-                // rows p, q of G <- J'G (lane = column): (g_p, g_q) <- (c g_p - s g_q, s g_p + c g_q)
-                if (lane < nf) {
-                    for (int t = 0; t < half; ++t) {
-                        const int p = pp[t], q = pq[t];
-                        if (p == q) continue;
-                        const double cs = rc[t], sn = rs[t];
-                        const double gp = G[p * S + lane], gq = G[q * S + lane];
-                        G[p * S + lane] = cs * gp - sn * gq;
-                        G[q * S + lane] = sn * gp + cs * gq;
-                    }
-                }
-                wave_sync();
-                // columns p, q of G <- G J and of V <- V J (lane = row)
-                if (lane < nf) {
-                    for (int t = 0; t < half; ++t) {
-                        const int p = pp[t], q = pq[t];
-                        if (p == q) continue;
-                        const double cs = rc[t], sn = rs[t];
-                        const double gp = G[lane * S + p], gq = G[lane * S + q];
-                        G[lane * S + p] = cs * gp - sn * gq;
-                        G[lane * S + q] = sn * gp + cs * gq;
-                        const double vp = NV[lane * S + p], vq = NV[lane * S + q];
-                        NV[lane * S + p] = cs * vp - sn * vq;
-                        NV[lane * S + q] = sn * vp + cs * vq;
-                    }
-                }
-                wave_sync();
-            }
-        }
-    }
-#endif
     // ---- singular values, descending; ksv = min(m, nf) of them exist (svd.singularValues(), Eigen's thin count)
     NHQP_PHASE("w:jacobi");
     const int ksv = (m < nf) ? m : nf;
@@ -2196,7 +2011,6 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare_wide_kernel(const DevNhq
         wave_sync();
     }
     const double sv_max = sig[0];
-    constexpr double kSvNoise = 1.0e-7;
     NHQP_PHASE("w:sort");
     // ---- regularize_A_b (nHQP.cpp:236-279)
     if (Q.ab_reg) {
@@ -2206,7 +2020,6 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare_wide_kernel(const DevNhq
         wave_sync();
         // U[:, i] = A N v_i / |A N v_i| where the triplet is genuine; a null triplet's u_i completes the basis: the first unit
         // vector with a usable component outside the span of the u's found so far (modified Gram-Schmidt, lane = row)
-#ifndef OSOT_NHQP_WIDE_U_VALU
         // (round 5) all genuine triplets at once: T = A N V on the fp64 matrix core with the columns of V gathered in singular-value
         // order (column j of T belongs to idx[j]), then lane = triplet for the norms, u_j'b0, the scaling and the lifting rule; the
         // null triplets (none on a full-rank level) are completed one by one afterwards as before.  Was one triplet after the other:
@@ -2300,52 +2113,6 @@ __global__ void __launch_bounds__(64) osot_nhqp_prepare_wide_kernel(const DevNhq
             done |= 1ull << i;
             wave_sync();
         }
-#else
-        int next_unit = 0;
-        for (int i = 0; i < ksv; ++i) {
-            const int ec = idx[i];
-            double u = 0.0;
-            bool have = false;
-            if (sig[i] >= kSvNoise * sv_max && sig[i] > 0.0) {
-                {   // (columns of A N and rows of V beyond nf are zero up to the next multiple of eight: whole chunks, eight reads in flight)
-                    const int rl = (lane < m) ? lane : 0;
-                    double u0 = 0.0, u1 = 0.0;
-                    for (int t = 0; t < nf; t += 8) {
-                        double a8[8], v8[8];
-#pragma unroll
-                        for (int q = 0; q < 8; ++q) { a8[q] = AN[rl * S + t + q]; v8[q] = NV[(t + q) * S + ec]; }
-#pragma unroll
-                        for (int q = 0; q < 8; q += 2) { u0 = fma(a8[q], v8[q], u0); u1 = fma(a8[q + 1], v8[q + 1], u1); }
-                    }
-                    u = (lane < m) ? u0 + u1 : 0.0;
-                }
-                const double nrm2 = uniform_d(colsum<64>(u * u));
-                if (nrm2 > 0.0) { u = u / sqrt(nrm2); have = true; }
-            }
-            while (!have && next_unit < m) {
-                u = (lane == next_unit) ? 1.0 : 0.0;
-                next_unit++;
-                for (int pass = 0; pass < 2; ++pass)
-                    for (int j = 0; j < i; ++j) {
-                        const double uj = (lane < m) ? U[lane * S + j] : 0.0;
-                        const double dot = uniform_d(colsum<64>(uj * u));
-                        u = fma(-dot, uj, u);
-                    }
-                const double nrm2 = uniform_d(colsum<64>(u * u));
-                if (nrm2 > 0.25) { u = u / sqrt(nrm2); have = true; }
-            }
-            if (!have) u = 0.0;
-            wave_sync();
-            if (lane < m) U[lane * S + i] = u;
-            const double dotb = uniform_d(colsum<64>((lane < m) ? u * b0[lane] : 0.0));
-            const double sv = sig[i];
-            const bool lift = sv < Q.thr * sv_max;
-            double d = 1.0, svn = sv;
-            if (lift) { d = sv / (Q.thr * sv_max); svn = (Q.thr * sv_max) * (Q.thr * sv_max) / (sv + Q.thr / 100.0); }
-            if (lane == 0) { ub[i] = d * dotb; dl[i] = lift ? svn - sv : 0.0; }
-            wave_sync();
-        }
-#endif
         // b0 <- sum_i d_i (u_i'b0) u_i  (U diag(d) U'b0 with b0_rot(i) = 0 beyond the ksv singular values)
         if (lane < m) {
             double v = 0.0;
@@ -2494,8 +2261,7 @@ __global__ void __launch_bounds__(64) osot_nhqp_accumulate_kernel(const DevNhqpA
         double* Nn = Q.Nnext + inst * (long long)n * n;
         // N V2 (n x ns).  Levels below the first: on the fp64 matrix core, operands straight from HBM / L2 (round 5: acc_tile_product --
         // one entry per lane through the vector unit issued 2 nf gathered loads per entry, 1400 per lane on the 35-coordinate COMAN;
-        // OSOT_NHQP_ACC_VALU keeps that form for A/B).  First level (N = I): the rows of V2 are copied.
-#ifndef OSOT_NHQP_ACC_VALU
+        // that form is in the history).  First level (N = I): the rows of V2 are copied.
         if (!Q.first) {
             const int MB = uniform_i((n + 15) >> 4);
             if (MB <= 1) acc_tile_product<1>(Ng, Vg, Nn, n, nf, ns, lane);
@@ -2504,21 +2270,9 @@ __global__ void __launch_bounds__(64) osot_nhqp_accumulate_kernel(const DevNhqpA
             else acc_tile_product<4>(Ng, Vg, Nn, n, nf, ns, lane);
             return;
         }
-#endif
         for (int e = lane; e < n * ns; e += 64) {
             const int i = e / ns, t = e - i * ns;
-            double a2 = 0.0;
-            if (Q.first) a2 = (i < nf) ? Vg[i * n + t] : 0.0;
-            else {
-                for (int j0 = 0; j0 < nf; j0 += 8) {
-                    double a[8], b[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) { const int j = j0 + u, jc = (j < nf) ? j : nf - 1; a[u] = Ng[i * n + jc]; b[u] = Vg[jc * n + t]; }
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) a2 = fma((j0 + u < nf) ? a[u] : 0.0, b[u], a2);
-                }
-            }
-            Nn[i * n + t] = a2;
+            Nn[i * n + t] = (i < nf) ? Vg[i * n + t] : 0.0;
         }
     }
 }

@@ -17,6 +17,7 @@
 #pragma once
 #include <cmath>
 #include <cstddef>
+#include "osot_qp_tol.h"   // kInfty, kViolTol, kEqTol, ...: the wavefront core's tolerances, by the same names
 
 #if defined(__HIPCC__) && !defined(OSOT_BIG_HOST)
 #define OSOT_BIG_FN __device__ inline
@@ -29,11 +30,6 @@ namespace big {
 
 constexpr int kMaxVars = 128;
 constexpr int kMaxRows = 2048;
-constexpr double kInf = 1.0e20;       // QPOasesBackEnd::checkINFTY clamp (QPOasesBackEnd.cpp:339-356)
-constexpr double kViol = 1.0e-11;     // a slack below -kViol max(1, |bound|) counts as violated         (osot_qp_core.h: kViolTol)
-constexpr double kEq = 1.0e-9;        // consistency of a linearly dependent equality row                (kEqTol)
-constexpr double kDep2 = 1.0e-24;     // |d2|^2 <= kDep2 |d|^2: the normal is in the span of the working set (kDepTol2)
-constexpr double kRatio = 1.0e-14;    // dual ratio test: r_k counts as positive above this fraction of max |r| (kRatioTol)
 enum { ST_SOLVED = 0, ST_INFEASIBLE = 1, ST_MAX_ITER = 2, ST_NOT_PD = 3 };   // = OSOT_STATUS_*
 
 struct Args {                         // one instance
@@ -47,22 +43,16 @@ struct Args {                         // one instance
     double* J;                        // workspace [n][n]: J = L^-T, rotated / reflected as the working set changes
     // cascade switch (osot_cascade_wide.h; the explicit-QP path leaves it off and keeps its statuses): a dependent equality that is
     // inconsistent, or a violated constraint with no direction left and no multiplier to trade, is accepted as round-off of the levels
-    // above when the violation is at most min(kSlackRel max(1, |bound|), kSlackCap); the largest one goes to *slack (thread 0)
+    // above when the violation is at most min(kSlackTol max(1, |bound|), kSlackCap); the largest one goes to *slack (thread 0)
     // With the switch on, the rest of the wavefront cascade's rule (osot_qp_core.h, gi_inequalities) comes along: an accepted bound or
     // row is RELAXED by 1.001 x the violation for the rest of the instance's cascade (lmut / umut: the box the cascade hands in as l / u;
     // rows: Rows::relax), so that the levels below accept the same point; a violation of at most kSpanAccept with its normal in the span
     // of the working set is accepted ahead of a dual exchange; and up to kRefineMax times per level the round-off of the ITERATE is taken
-    // out first (x += J1 y with R'y = the working set's residuals) before a violation up to kSlackRel is accepted.
+    // out first (x += J1 y with R'y = the working set's residuals) before a violation up to kSlackTol is accepted.
     bool accept_slack = false;
     double* slack = nullptr;
     double *lmut = nullptr, *umut = nullptr;
 };
-constexpr double kSlackRel = 1.0e-6;  // (osot_qp_core.h: kSlackTol, kSlackCap, kSpanAccept, kRefineFloor, kRefineMax)
-constexpr double kSlackCap = 1.0e-5;
-constexpr double kSpanAccept = 1.0e-8;
-constexpr double kRefineFloor = 1.0e-9;
-constexpr int kRefineMax = 2;
-constexpr double kDepFloor2 = 1.0e-13;   // second dependence test of the cascade, where |d2|^2 <= 1e-12 |d|^2 (osot_qp_core.h: kDepFloor2)
 
 // The constraint rows as the solver sees them.  DenseRows: the explicit QP's A [nc][n] with lA <= A x <= uA.  A row source must
 // give the clamped bounds, a'x, and either the row's n coefficients or the variable of a unit row e_col (osot_cascade_wide.h: rows
@@ -120,7 +110,7 @@ OSOT_BIG_FN Shared carve(void* base, int n, int nc) {
     return s;
 }
 
-OSOT_BIG_FN double clamp_inf(double v) { return v >= kInf ? kInf : (v <= -kInf ? -kInf : v); }
+OSOT_BIG_FN double clamp_inf(double v) { return v >= kInfty ? kInfty : (v <= -kInfty ? -kInfty : v); }
 OSOT_BIG_FN int ridx(int i, int j) { return ((j * (j + 1)) >> 1) + i; }
 OSOT_BIG_FN double DenseRows::lo(int r) const { return clamp_inf(lA[r]); }
 OSOT_BIG_FN double DenseRows::up(int r) const { return clamp_inf(uA[r]); }
@@ -209,7 +199,7 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
         // cascade: a normal at 1e-6 of the span of the working set is a direction on paper only -- taking it puts |d2| on the diagonal
         // of R and moves x by violation / |d2|.  Per FREE column c of J: d_c^2 / (|J_c|^2 |n|^2) = cos^2 of its angle with the normal;
         // no usable angle with any of them: dependent (osot_qp_core.h: direction_is_independent)
-        if (a.accept_slack && !(s.sc[SD_ND2] > 1.0e-12 * s.sc[SD_DD]) && s.sc[SD_ND2] > kDep2 * s.sc[SD_DD]) {
+        if (a.accept_slack && !(s.sc[SD_ND2] > 1.0e-12 * s.sc[SD_DD]) && s.sc[SD_ND2] > kDepTol2 * s.sc[SD_DD]) {
             OSOT_BIG_FOR(c, n) {
                 double cos2 = 0.0;
                 if (c >= iq) {
@@ -301,9 +291,9 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
         if (t0) { s.sc[SD_SIP] = rows.dot(r, s.x) - lo; s.rstate[r] = 3; }
         compute_d(n + r, +1);
         const double nd2 = s.sc[SD_ND2], dd = s.sc[SD_DD], sip = s.sc[SD_SIP];
-        if (!(nd2 > kDep2 * dd)) {                       // a combination of the rows already in
-            if (fabs(sip) > kEq * fmax(1.0, fabs(lo))) {
-                if (a.accept_slack && fabs(sip) <= fmin(kSlackRel * fmax(1.0, fabs(lo)), kSlackCap)) {   // round-off of the levels above
+        if (!(nd2 > kDepTol2 * dd)) {                    // a combination of the rows already in
+            if (fabs(sip) > kEqTol * fmax(1.0, fabs(lo))) {
+                if (a.accept_slack && fabs(sip) <= fmin(kSlackTol * fmax(1.0, fabs(lo)), kSlackCap)) {   // round-off of the levels above
                     tm.sync();
                     if (t0) s.sc[SD_SLACK] = fmax(s.sc[SD_SLACK], fabs(sip));
                     continue;
@@ -329,8 +319,8 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
             double v = 0.0; int sd = 0;
             if (has_box && s.bstate[k] == 0) {
                 const double lo = clamp_inf(a.l[k]), up = clamp_inf(a.u[k]), xk = s.x[k];
-                if (lo > -kInf) { const double vi = lo - xk; if (vi > kViol * fmax(1.0, fabs(lo)) && vi > v) { v = vi; sd = +1; } }
-                if (up < kInf) { const double vi = xk - up; if (vi > kViol * fmax(1.0, fabs(up)) && vi > v) { v = vi; sd = -1; } }
+                if (lo > -kInfty) { const double vi = lo - xk; if (vi > kViolTol * fmax(1.0, fabs(lo)) && vi > v) { v = vi; sd = +1; } }
+                if (up < kInfty) { const double vi = xk - up; if (vi > kViolTol * fmax(1.0, fabs(up)) && vi > v) { v = vi; sd = -1; } }
             }
             s.cval[k] = v; s.cside[k] = sd;
         }
@@ -338,10 +328,10 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
             double v = 0.0; int sd = 0;
             if (s.rstate[r] == 0) {
                 const double lo = rows.lo(r), up = rows.up(r);
-                if (lo > -kInf || up < kInf) {
+                if (lo > -kInfty || up < kInfty) {
                     const double ax = rows.dot(r, s.x);
-                    if (lo > -kInf) { const double vi = lo - ax; if (vi > kViol * fmax(1.0, fabs(lo)) && vi > v) { v = vi; sd = +1; } }
-                    if (up < kInf) { const double vi = ax - up; if (vi > kViol * fmax(1.0, fabs(up)) && vi > v) { v = vi; sd = -1; } }
+                    if (lo > -kInfty) { const double vi = lo - ax; if (vi > kViolTol * fmax(1.0, fabs(lo)) && vi > v) { v = vi; sd = +1; } }
+                    if (up < kInfty) { const double vi = ax - up; if (vi > kViolTol * fmax(1.0, fabs(up)) && vi > v) { v = vi; sd = -1; } }
                 }
             }
             s.cval[n + r] = v; s.cside[n + r] = sd;
@@ -375,18 +365,18 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
                 for (int k = me; k < iq; ++k) rmax = fmax(rmax, fabs(s.r[k]));
                 double t1 = INFINITY; int l = -1;
                 for (int k = me; k < iq; ++k)
-                    if (s.r[k] > kRatio * rmax && s.r[k] > 0.0) { const double q = s.u[k] / s.r[k]; if (q < t1) { t1 = q; l = k; } }
+                    if (s.r[k] > kRatioTol * rmax && s.r[k] > 0.0) { const double q = s.u[k] / s.r[k]; if (q < t1) { t1 = q; l = k; } }
                 const double nd2 = s.sc[SD_ND2], dd = s.sc[SD_DD], sip = s.sc[SD_SIP];
-                const bool has_dir = nd2 > kDep2 * dd;
+                const bool has_dir = nd2 > kDepTol2 * dd;
                 const double t2 = has_dir ? -sip / nd2 : INFINITY;
                 int act; double t = 0.0;
                 const double viol = -sip, bmag = fmax(1.0, fabs(s.sc[SD_BND]));
                 const bool refine = a.accept_slack && s.si[SI_REFINE] > 0;
                 if (a.accept_slack && !has_dir && t1 < INFINITY && viol <= kSpanAccept * bmag) act = 5;     // round-off ahead of an exchange: accept
-                else if (refine && !has_dir && t1 < INFINITY && viol <= kSlackRel * bmag) act = 6;          // ... or refine the iterate first
+                else if (refine && !has_dir && t1 < INFINITY && viol <= kSlackTol * bmag) act = 6;          // ... or refine the iterate first
                 else if (!(t1 < INFINITY) && !(t2 < INFINITY)) {                                           // no step at all: infeasible, or
                     act = 0;                                                                                // round-off of the levels above
-                    if (a.accept_slack && viol <= fmin(kSlackRel * bmag, kSlackCap)) act = (refine && viol > kRefineFloor * bmag) ? 6 : 5;
+                    if (a.accept_slack && viol <= fmin(kSlackTol * bmag, kSlackCap)) act = (refine && viol > kRefineFloor * bmag) ? 6 : 5;
                 }
                 else if (t2 <= t1) { act = 2; t = t2; }                                    // full step: ip enters
                 else if (!has_dir) { act = 1; t = t1; }                                    // dual step only: l leaves

@@ -25,42 +25,15 @@
 //     M2[NP][S]  JT, JT[j][k] = J[k][j]  (starts as L^-1; or the closed-form J of a low-rank level, or the
 //                H-orthonormal null-space basis of the equality rows under a diagonal Hessian)
 // H itself never sits in LDS: it is built and factorised in registers (NP = 32: in the accumulator layout of
-// v_mfma_f64_16x16x4_f64, factor_tiles32; NP = 64: one column per lane, factor_rows64).
+// v_mfma_f64_16x16x4_f64, factor_tiles32; NP > 32: the upper triangle of 16 x 16 tiles, factor_tiles_wide).
 //     V[4][LW]   staging vectors for broadcasts
 // All control flow is wave-uniform.
 #pragma once
 #include <osot_team.h>  // resolved through -I: csrc/ for the product, tests/emu/ for the host emulation
+#include "osot_qp_tol.h" // kInfty, kViolTol, ... : the active-set tolerances, shared with osot_qp_big.h
 
 namespace osot {
 
-constexpr double kInfty = 1.0e20;      // QPOasesBackEnd::checkINFTY clamp (QPOasesBackEnd.cpp:339-356)
-constexpr double kDepTol2 = 1.0e-24;   // |d2|^2 <= kDepTol2 |d|^2  -> normal is in the span of the working set.
-                                       // |d|^2 is dominated by the 1/eps-scaled directions (6e10 at the default eps), the
-                                       // round-off floor of |d2|^2 is ~1e-29 |d|^2, and a genuine last free direction was seen
-                                       // at 6e-19 |d|^2 (tests/stress_parity.py): 1e-18 called it dependent -> false INFEASIBLE
-constexpr double kDepFloor2 = 1.0e-13; // second test, only when |d2|^2 <= 1e-12 |d|^2: max over the free columns c of J of
-                                       // d2_c^2 / (|J_c|^2 |n|^2) <= kDepFloor2 -> dependent (see direction_is_independent).
-                                       // That ratio is the cos^2 of the angle between the normal and the column: about the
-                                       // sine^2 of its angle with the span of the working set.  A row at 1e-8 .. 1e-12 of that span is a direction on paper, but
-                                       // taking it puts |d2| on the diagonal of R (condition 1e8+: the dual directions r lose
-                                       // their signs) and moves x by violation / |d2|.  Seen on hardware (closed-loop
-                                       // self-collision tests, H ~ I): sine^2 = 3e-23 with a bound violated by 4e-11 -> x jumped
-                                       // by 26; sine^2 = 1.5e-17 with 1e-7 -> by 14; both ended as false INFEASIBLE.  The genuine
-                                       // last direction quoted above sits at 9.4e-9 on this scale.  tests/stress_closed_loop.py:
-                                       // 5.3 M closed-loop solves at eps factor 1e6 without an unsolved instance (346 in
-                                       // 921 k with a floor of 1e-19); at the default eps 5 distinct instances in 3 x 307 k
-constexpr double kViolTol = 1.0e-11;   // a slack below -kViolTol*max(1,|bound|) counts as violated
-constexpr double kEqTol = 1.0e-9;      // consistency of a linearly dependent equality row
-constexpr double kSlackTol = 1.0e-6;   // a violation below this (relative) with no direction left is round-off: with the
-                                       // default eps (4.4e-11) an upper level's x carries O(1e-16 / eps) = 1e-6 of noise and
-                                       // its active bound re-appears violated by that much where no freedom is left
-                                       // (found by tests/stress_parity.py; qpOASES accepts the same point)
-
-#ifndef OSOT_RATIO_TOL
-#define OSOT_RATIO_TOL 1.0e-14
-#endif
-constexpr double kRatioTol = OSOT_RATIO_TOL;  // (1e-10 cost a genuine trade at the default eps, where the entries of r span ten decades; the noise seen was < 1e-15)  // dual ratio test: r_k counts as positive only above this fraction of max |r| (see gi_inequalities)
-constexpr double kSlackCap = 1.0e-5;   // ... but never more than this in absolute terms (torque / acceleration limits of 1e2 .. 1e3)
 #ifndef OSOT_FEAS_MARGIN
 #define OSOT_FEAS_MARGIN 0.0
 #endif
@@ -77,17 +50,14 @@ constexpr double kFeasMargin = OSOT_FEAS_MARGIN;  // cascade levels below the fi
 enum { QP_SOLVED = 0, QP_INFEASIBLE = 1, QP_MAX_ITER = 2, QP_NOT_PD = 3 };
 
 // R (the triangular factor of the working set; upper Hessenberg for a moment while a constraint is being dropped) lives in
-// M1, PACKED by columns, column j holding rows 0 .. j+1 at offset j (j + 3) / 2 (NP = 64, round 3: 17 KB instead of 33, with the
-// Cholesky factor L of factor_rows64 packed by rows in the same slice and the row table moved out of LDS: 52 KB per wave, three
-// waves per CU instead of two).  NP = 32: 560 doubles instead of 1056: the 4 KB that let ten
+// M1, PACKED by columns, column j holding rows 0 .. j+1 at offset j (j + 3) / 2 (NP = 64, round 3: 17 KB instead of 33, and
+// the row table moved out of LDS: 52 KB per wave, three waves per CU instead of two).  NP = 32: 560 doubles instead of 1056: the 4 KB that let ten
 // waves (instead of eight) share a CU's 160 KB of LDS, i.e. 2560 instead of 2048 instances in flight.  (At BASELINE
 // config 3 a batch of 4096 then is 1.6 instead of 2 jobs per slot: the long jobs get a slot to themselves and the launch
 // ends with its longest instance instead of with a late-started short one; tools/prof_cycle.py shows the timeline.)  A
 // column's rows are contiguous, so lane-per-row accesses of one column are conflict-free and the column offset is uniform.
 template <int NP>
 __device__ __forceinline__ int ridx(int i, int j) { return ((j * (j + 3)) >> 1) + i; }   // (round 3: packed for NP = 64 as well)
-// the Cholesky factor L of the 64-lane path, PACKED by rows (row i holds columns 0 .. i) in the same M1 slice
-__device__ __forceinline__ int lidx(int i, int j) { return ((i * (i + 1)) >> 1) + j; }
 template <int NP>
 struct WaveCtx {
     // NP = padded problem size: 32 (two lanes per column), 64, or 56 -- the 64-lane solver with its LDS cut to what n <= 54
@@ -103,8 +73,8 @@ struct WaveCtx {
     static constexpr bool PH = (NP > 32 && NP < 64);
     static constexpr int ROWS = PH ? NP + 1 : NP;          // rows of M2 that exist
     static constexpr int NMAX = PH ? NP - 2 : NP;          // largest n of this instantiation
-    // packed R: 560 doubles for NP = 32, 2144 for NP = 64 (the packed L of factor_rows64, 2080, fits too); NP = 56: the packed
-    // L of the 56 padded rows, 1596 (R of n <= 54 columns needs 1539)
+    // packed R: 560 doubles for NP = 32, 2144 for NP = 64; the phantom layouts keep the NP (NP + 1) / 2 of the packed Cholesky
+    // factor of round 3's register row sweep (in the history): 1596 for NP = 56, where R of n <= 54 columns needs 1539
     static constexpr int M1_DOUBLES = PH ? (NP * (NP + 1)) / 2 : NP * (NP + 3) / 2;
     // elements in flight per trip of the mat-vec passes / the stored-row walk (divisors of NP, multiples of 4)
 #ifndef OSOT_DOT_CH40
@@ -450,37 +420,22 @@ __device__ inline int factor_tiles32(const WaveCtx<32>& w, double (&Hf)[16], dou
             const int j = 4 * p + qq;
             const int lj = (4 * rp + qq) + 16 * qq;   // lane (a = j & 15, q = qq) holds H[j][j] in Pn[Ip]
             double piv = bcast(Pn[Ip], lj);
-#ifdef OSOT_X_OLD_CHOL32
-            if (!(piv > 0.0)) { bad = true; piv = 1.0; }
-#else
             bad = bad || !(piv > 0.0);      // (a non-positive or NaN pivot poisons what follows; the routine returns NOT_PD and x = 0 then)
-#endif
             double sq, rs;
             fast_sqrt_rsqrt(piv, sq, rs);
             rsq[qq] = rs;
             const bool mine = (tq == qq);
-#ifdef OSOT_X_OLD_CHOL32
-#pragma unroll
-            for (int X = 0; X < 2; ++X) {
-                const int i = 16 * X + ta;
-                const double scaled = (i > j) ? Pn[X] * rs : ((i == j) ? sq : 0.0);
-                Pn[X] = mine ? scaled : Pn[X];
-                Rp[X] = mine ? Rp[X] * rs : Rp[X];
-            }
-#else
             // Round 6 (instruction diet): the column's quarter-row is scaled by ONE masked multiplier (1 / L[j][j] in the lanes that hold
             // it, 1 elsewhere) instead of three selects per register.  The entries on and above the diagonal are NOT cleared here -- by
             // symmetry they hold the upper triangle of the trailing matrix, which nothing below reads: the later columns of the panel take
             // L[4p + q][j] from BELOW the diagonal, the trailing products mask the rows of the panel, and the forward substitution's
             // staging clears them once per panel (below).  The entries below the diagonal get the same bits as before.
-            (void)sq;
             const double mul = mine ? rs : 1.0;
 #pragma unroll
             for (int X = 0; X < 2; ++X) {
                 if (!(Ip == 1 && X == 0)) Pn[X] *= mul;
                 if (!(Ip == 0 && X == 1)) Rp[X] *= mul;
             }
-#endif
             if (qq < 3) {
                 const int src = ta + 16 * qq;                     // lane (a, qq): same row, column j
                 const double ljj = __shfl(Pn[Ip], (4 * rp + tq) + 16 * qq, 64);   // L[4p + q][j] for my column 4p + q
@@ -499,15 +454,10 @@ __device__ inline int factor_tiles32(const WaveCtx<32>& w, double (&Hf)[16], dou
             }
         }
         // finished panel (zeros above the diagonal included) -> staging; final rows of L^-1 back into their tiles
-#ifdef OSOT_X_OLD_CHOL32
-        PB[tq * 32 + ta] = Pn[0];
-        PB[tq * 32 + 16 + ta] = Pn[1];
-#else
         // staged with zeros ON and above the diagonal (column 4p + tq at rows ta, 16 + ta): a step of the substitution below is then a
         // plain fma in every lane -- rows at or above the column see a zero and keep their residual
         PB[tq * 32 + ta] = (Ip == 0 && ta > 4 * p + tq) ? Pn[0] : 0.0;
         PB[tq * 32 + 16 + ta] = (16 + ta > 4 * p + tq) ? Pn[1] : 0.0;
-#endif
         if (Ip) { L10[rp] = Rp[0]; L11[rp] = Rp[1]; } else { L00[rp] = Rp[0]; }
         wave_sync();
         {   // forward substitution through the panel's four columns: y_j = rhs_j / L[j][j], rhs_i -= L[i][j] y_j below it
@@ -518,11 +468,7 @@ __device__ inline int factor_tiles32(const WaveCtx<32>& w, double (&Hf)[16], dou
             for (int qq = 0; qq < 4; ++qq) {
                 const int j = 4 * p + qq;
                 const double yj = bcast(rhs, j) * rsq[qq];
-#ifdef OSOT_X_OLD_CHOL32
-                rhs = (c == j) ? yj : ((c > j) ? fma(-lrow[qq], yj, rhs) : rhs);
-#else
                 rhs = fma(-lrow[qq], yj, rhs);      // (lane j keeps its residual: y_j = rhs_j / L[j][j] is formed from it at the end)
-#endif
             }
         }
         wave_sync();   // the staging buffer is free for the next panel
@@ -554,12 +500,10 @@ __device__ inline int factor_tiles32(const WaveCtx<32>& w, double (&Hf)[16], dou
     OSOT_TT(1);   // L^-1 store
     OSOT_TT(2);   // (forward substitution: done panel by panel above)
     // L'x = y:  x_c = sum_j (L^-1)[j][c] y_j  (rhs holds y; rows of L^-1 = rows of JT)
-#ifndef OSOT_X_OLD_CHOL32
     // y_c = (residual of row c) / L[c][c]: the reciprocal is the diagonal of L^-1 that has just been stored -- the very value the
     // substitution multiplied by when it broadcast y_c (a row of L^-1 starts as a unit row, is scaled once, by 1 / L[c][c], and no
     // later update reaches its diagonal: exact)
     rhs *= M2[c * S + c];
-#endif
     if (w.h == 0) w.V[c] = valid ? rhs : 0.0;
     wave_sync();
     const double x = jt_cols_dot<32>(w, w.V);
@@ -574,20 +518,14 @@ __device__ inline int factor_tiles32(const WaveCtx<32>& w, double (&Hf)[16], dou
 // Round 5: the SAME blocked factorisation for the 64-lane layouts (NP = 40 / 56 / 64: 33 .. 64 variables) on T x T tiles of
 // 16 x 16 (T = 3 covers 48 columns, T = 4 covers 64).  H + eps I arrives as the UPPER triangle of tiles (T (T + 1) / 2 of them,
 // tile_u), L^-1 is built as the LOWER triangle (tile_l): 24 + 24 fp64 registers for T = 3, 40 + 40 for T = 4, where the
-// register-resident row sweep (factor_rows64 below) holds NP-register arrays whose fully unrolled sweeps the allocator answers
-// with 50 .. 300 spilled registers (profiles/r05_v1_kernel_resources.txt).  Panel p = columns 4p .. 4p+3 is element p & 3 of the
+// register-resident row sweep it replaced (in the history) held NP-register arrays whose fully unrolled sweeps the allocator
+// answered with 50 .. 300 spilled registers (profiles/r05_v1_kernel_resources.txt).  Panel p = columns 4p .. 4p+3 is element p & 3 of the
 // tiles (p >> 2, X), X >= p >> 2; the trailing updates are one MFMA per live tile.  Panels that lie entirely in the identity
 // padding beyond n (only possible from p = 8 on: these layouts serve n > 32) are skipped under a uniform guard: the padding
 // factorises to itself and no earlier panel reaches it (its off-diagonal entries are zero).
 // In : Hf[4 tile_u(I, C) + r] = (H + eps I)[16 I + q + 4 r][16 C + a] with a unit diagonal beyond n, lane (a, q) = (lane & 15,
 // lane >> 4) of the PHYSICAL lane; g by lane = column.  Out: M2 = JT = L^-1 (identity on the padding n .. NP-1, nothing at or
 // beyond NP), x = -(H + eps I)^-1 g by substitution (forward panel by panel, backward as (L^-1)'y); M1 clobbered.
-// the 64-lane layouts factorise on tiles (factor_tiles_wide); OSOT_X_ROWS64 brings back the register row sweep (A/B builds)
-#ifdef OSOT_X_ROWS64
-constexpr bool kWideTiles = false;
-#else
-constexpr bool kWideTiles = true;
-#endif
 constexpr int wide_tiles(int np) { return np <= 48 ? 3 : 4; }      // 16 x 16 tiles per side: NP = 40 -> 3, NP = 56 / 64 -> 4
 template <int P, int N, class F>
 __device__ __forceinline__ void static_for(F& f) {       // f(integral_constant<int, P>) for P = P .. N-1, each a compile-time call
@@ -713,120 +651,6 @@ __device__ __forceinline__ int factor_tiles_wide(const WaveCtx<NP>& w, double (&
     return QP_SOLVED;
 }
 
-// NP = 64 (one lane per column, 64 registers per array): a LEFT-looking, row-oriented variant in two passes so
-// that only ONE 64-register array is live at a time (the right-looking sweep above needs H and L^-1 together:
-// 256 VGPRs before any temporaries).  By symmetry lane c's column of H is its ROW c, so
-//   pass 1 (Cholesky, in place):  L[c][j] = (H[c][j] - sum_{k<j} L[c][k] L[j][k]) / L[j][j]
-//     lane c's own row L[c][k] sits in the registers Hc[k] it has already overwritten (static index); row j of
-//     L is complete in LDS after step j-1 and is read with UNIFORM addresses (LDS broadcast, ds_read2_b64);
-//     no reduction: only the pivot is broadcast with v_readlane.  The forward substitution rides along.
-//   pass 2 (inverse by rows):  Linv[i][c] = (delta_ic - sum_{k<i} L[i][k] Linv[k][c]) / L[i][i]
-//     the same shape, no cross-lane step at all (pure ILP, four accumulators per dot product).
-// The row bases are laundered: ds_read2_b64 only has an 8-bit offset field, so without it every pair of reads
-// gets its own constant address, and loop-invariant code motion parks ~900 of them in (spilled) SGPRs.
-// In : Hc[i] = (H + eps I)[i][c] (lane c owns column c = row c), g.  Out: M1 = L, M2 = JT = L^-1, x = -(H + eps I)^-1 g.  MUST be inlined (Hc would otherwise travel through scratch by reference).
-template <int NP, bool FULL>
-__device__ __forceinline__ int factor_rows64(const WaveCtx<NP>& w, double (&Hc)[NP], double g, double& x_out) {
-    constexpr int S = WaveCtx<NP>::S;   // (NP = 64 or 56; the phantom lanes of NP = 56 hold zeros and store nothing into M1)
-    const int c = w.c, n = w.n;
-    const bool valid = FULL || (c < n);
-    double* M1 = w.M1;
-    double* M2 = w.M2;
-    double rhs = valid ? -g : 0.0;
-    double invd = 0.0;
-    bool bad = false;
-    // Control flow is kept to ONE uniform guard per block of eight columns and no early exit (a guard or an
-    // exit per column gives the register allocator 64 join points and ~3000 spills): the caller pads H with
-    // a unit diagonal beyond n, so the columns n .. roundup8(n)-1 factorise to the identity.
-#pragma unroll
-    for (int j0 = 0; j0 < NP; j0 += 8) {
-        if (FULL || j0 < n) {
-#pragma unroll
-            for (int j = j0; j < j0 + 8; ++j) {
-                double acc[4] = {Hc[j], 0.0, 0.0, 0.0};
-                const double* rowj = M1 + launder_i(lidx(j, 0));   // opaque base: see the note on LDS addresses
-#pragma unroll
-                for (int q = 0; q < (NP + 15) / 16; ++q) {
-                    if (16 * q < j) {
-                        double lj[16];
-#pragma unroll
-                        for (int t = 0; t < 16; ++t) if (16 * q + t < j) lj[t] = rowj[16 * q + t];
-#pragma unroll
-                        for (int t = 0; t < 16; ++t) if (16 * q + t < j) acc[t & 3] = fma(-Hc[16 * q + t], lj[t], acc[t & 3]);
-                    }
-                }
-                const double sres = (acc[0] + acc[1]) + (acc[2] + acc[3]);
-                double piv = bcast(sres, j);
-                if (!(piv > 0.0)) { bad = true; piv = 1.0; }
-                double sq, rs;
-                fast_sqrt_rsqrt(piv, sq, rs);
-                const double lcj = (c == j) ? sq : ((c > j) ? sres * rs : 0.0);
-                Hc[j] = lcj;
-                if (c >= j && c < NP) M1[lidx(c, j)] = lcj;   // (packed: the zeros above the diagonal are not stored)
-                if (c == j) invd = rs;
-                const double yj = bcast(rhs, j) * rs;                       // forward substitution
-                rhs = (c == j) ? yj : fma(-lcj, yj, rhs);
-                wave_sync();
-            }
-        }
-    }
-    if (bad) { x_out = 0.0; return QP_NOT_PD; }
-    // pass 2: JT = L^-1, row by row; Hc is dead from here on.  1/L[i][i] goes through LDS (64 v_readlane
-    // results would all be hoisted to the top and spill the scalar file); a scheduling fence per row keeps
-    // the row reads from being hoisted wholesale (the rows are independent of everything but Lc).
-    w.V[c] = invd;
-    wave_sync();
-    {
-        double Lc[NP];
-#pragma unroll
-        for (int i0 = 0; i0 < NP; i0 += 8) {
-            if (FULL || i0 < n) {
-#pragma unroll
-                for (int i = i0; i < i0 + 8; ++i) {
-                    double acc[4] = {(i == c) ? 1.0 : 0.0, 0.0, 0.0, 0.0};
-                    const double* rowi = M1 + launder_i(lidx(i, 0));
-#pragma unroll
-                    for (int q = 0; q < (NP + 15) / 16; ++q) {
-                        if (16 * q < i) {
-                            double li[16];
-#pragma unroll
-                            for (int t = 0; t < 16; ++t) if (16 * q + t < i) li[t] = rowi[16 * q + t];
-#pragma unroll
-                            for (int t = 0; t < 16; ++t) if (16 * q + t < i) acc[t & 3] = fma(-Lc[16 * q + t], li[t], acc[t & 3]);
-                        }
-                    }
-                    Lc[i] = ((acc[0] + acc[1]) + (acc[2] + acc[3])) * w.V[i];
-                    M2[i * S + c] = Lc[i];
-                    sched_fence();
-                }
-            } else {
-#pragma unroll
-                for (int i = i0; i < i0 + 8; ++i) { Lc[i] = (i == c) ? 1.0 : 0.0; M2[i * S + c] = Lc[i]; }
-            }
-        }
-    }
-    // backward substitution L'x = y (rhs holds y); rows of L are fetched eight at a time ahead of the chain
-    double x = 0.0;
-    const double yinv0 = invd;
-#pragma unroll
-    for (int i0 = NP - 8; i0 >= 0; i0 -= 8) {
-        if (FULL || i0 < n) {   // same block guard as above (the padded rows are identity rows)
-            double lrow[8];
-#pragma unroll
-            for (int t = 0; t < 8; ++t) { const double lv = M1[lidx(i0 + t, (c <= i0 + t) ? c : 0)]; lrow[t] = (c <= i0 + t) ? lv : 0.0; }   // zero for c > i; lane i itself is done
-#pragma unroll
-            for (int t = 7; t >= 0; --t) {
-                const int i = i0 + t;
-                const double xi = bcast(rhs * yinv0, i);
-                if (c == i) x = xi;
-                rhs = fma(-lrow[t], xi, rhs);
-            }
-        }
-    }
-    wave_sync();
-    x_out = valid ? x : 0.0;
-    return QP_SOLVED;
-}
 // phase cycle counters of the profiling instantiation (PROF = true): indices into prof[]
 enum { PH_HBUILD = 0, PH_CHOL = 1, PH_INV = 2, PH_SUBST = 3, PH_EQ = 4, PH_INEQ = 5, PH_OPT = 6, PH_TOTAL = 7,
        PH_EQ_D = 8, PH_EQ_RED = 9, PH_EQ_Z = 10, PH_EQ_HH = 11,
@@ -1334,11 +1158,6 @@ __device__ inline int nullspace_equalities_wide(const WaveCtx<NP>& w, int n_eq, 
 // measured against n'(J2 J2')n -- for a bound exactly the diagonal entry sum_s J2[c][s]^2, returned as hinv.
 // Returns the rank, or -1 (nothing the generic path relies on has been touched: it overwrites M1 and M2 itself) when more than
 // kDenseNullFree columns stay free, none does, or G is not positive definite.
-#ifndef OSOT_X_NO_DENSE_NULL40
-constexpr bool kDenseNull40 = true;
-#else
-constexpr bool kDenseNull40 = false;
-#endif
 constexpr int kDenseNullFree = 24;   // free columns carried (registers: the lane's row of Z)
 constexpr int kDenseNullRows = 24;   // stored rows of the level (their products with Z are staged in M1: 24 x 33 doubles)
 template <int NP, bool PROF>
@@ -1602,12 +1421,6 @@ __device__ inline bool direction_is_independent(const WaveCtx<NP>& w, double nd2
 // set at the current x (equalities: lo - a'x, or a'(x_prev - x) for an optimality row; active inequalities: minus their
 // slack), R'y = rho by forward substitution, x += J1 y -- the minimum-H-norm correction onto the manifold.  Cold path: a few
 // instances per thousand at the default eps, none at the benchmark's.
-#ifndef OSOT_REFINE_FLOOR
-#define OSOT_REFINE_FLOOR 1.0e-9
-#endif
-constexpr double kRefineFloor = OSOT_REFINE_FLOOR;   // violations below this (relative to max(1, |bound|)) are accepted without a refinement
-constexpr int kRefineMax = 2;             // refinements per level
-constexpr double kSpanAccept = 1.0e-8;    // (see gi_inequalities: a violation below this with the normal in the span of the working set is not exchanged)
 template <int NP, bool BOX>
 __device__ __forceinline__ double refine_on_working_set(const WaveCtx<NP>& w, double x, int iq, int Aq, double lb, double ub, double xprev) {
     const int c = w.c, h = w.h, n = w.n;
@@ -1674,11 +1487,6 @@ __device__ int gi_inequalities(const WaveCtx<NP>& w, int nrows, double x, int iq
 #define OSOT_LOWRANK_MAX 6      // round 5: one Cartesian task (six rows) next to a Postural block -- BASELINE config 2 -- takes the closed form too
 #endif
 constexpr int kLowRankMax = OSOT_LOWRANK_MAX;
-#ifndef OSOT_X_NO_LOWRANK40
-constexpr bool kLowRank40 = true;     // round 6: the closed form for the 40-lane layout as well (OSOT_X_NO_LOWRANK40: the factorisation, for A/B)
-#else
-constexpr bool kLowRank40 = false;
-#endif
 // MM = compile-time bound on the rows (3 for a CoM task, else kLowRankMax): the m x m algebra is fully unrolled
 // (round 6: NP = 32 as before, and NP = 40 -- the CoM level of the reference's COMAN stacks on its own 35-coordinate robot)
 template <int NP, int MM>
@@ -1830,8 +1638,8 @@ __device__ inline void lowrank_prepare(const WaveCtx<NP>& w, const double* Ak, c
     wave_sync();
 }
 
-// Pre (general H):  Hc = the accumulator tiles of H + eps I (NP = 32: factor_tiles32; NP > 32: the upper triangle of tiles, factor_tiles_wide;
-// with OSOT_X_ROWS64 Hc[ii] = (H + eps I)[ii][c] in registers, factor_rows64), M1 is scratch.
+// Pre (general H):  Hc = the accumulator tiles of H + eps I (NP = 32: factor_tiles32; NP > 32: the upper triangle of tiles, factor_tiles_wide),
+// M1 is scratch.
 template <int NP, bool PROF, bool BOX = false>
 __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_h,
                         double hdiag, double (&Hc)[NP / WaveCtx<NP>::HV], bool has_box, double& lb, double& ub, int max_iter,
@@ -1883,8 +1691,7 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
     } else {
         int stf;
         if constexpr (NP > 32) {
-            if constexpr (kWideTiles) stf = factor_tiles_wide<NP, wide_tiles(NP)>(w, Hc, g, x);
-            else stf = factor_rows64<NP, false>(w, Hc, g, x);
+            stf = factor_tiles_wide<NP, wide_tiles(NP)>(w, Hc, g, x);
         } else stf = factor_tiles32(w, Hc, g, x);
         stf = uniform_i(stf);
         if (stf != QP_SOLVED) { x_out = 0.0; iters_out = 0; return stf; }
@@ -1942,22 +1749,16 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
         wave_sync();
         iq = dense_rank; iters += dense_neq; used_nullspace = true;
     }
-#ifdef OSOT_X_NO_NULLSPACE
-    if (false) {
-#else
     if (NP == 32 && diag_h && have_prev && !local_eq && n_eq >= 8 && n_eq <= 32 && n - n_eq <= kNullMax) {
-#endif
         const int r_ns = uniform_i(nullspace_equalities32<PROF>(reinterpret_cast<const WaveCtx<32>&>(w), n_eq, hdiag, g, xprev, x, prof));
         if (r_ns >= 0) { iq = r_ns; iters += n_eq; used_nullspace = true; n_eq = 0; }
     }
-#ifndef OSOT_X_NO_NULLSPACE40
     if constexpr (NP == 40) {     // round 6: the 40-lane layout (the reference's 35-coordinate COMAN) takes the same route
         if (diag_h && have_prev && !local_eq && n_eq >= 8 && n_eq <= 32 && n - n_eq <= kNullMax) {
             const int r_ns = uniform_i(nullspace_equalities_wide<NP, PROF>(w, n_eq, hdiag, g, xprev, x, prof));
             if (r_ns >= 0) { iq = r_ns; iters += n_eq; used_nullspace = true; n_eq = 0; }
         }
     }
-#endif
     // (uniform_i / uniform_d below: table entries and reduction results ARE wave-uniform, said so that the loop's control flow
     // and its counters stay on the scalar unit -- see osot_team.h)
     // The equality rows are added IN PAIRS wherever two consecutive rows are both (clearly) independent of the working set: a pass
@@ -2296,12 +2097,7 @@ __device__ int gi_inequalities(const WaveCtx<NP>& w, int nrows, double x, int iq
         // Few stored rows (round 5; BASELINE config 4's sixteen collision rows): FOUR lanes per row, each a quarter of the columns --
         // the walk is one round trip of NP / 4 loads per lane and a two-stage quad reduction where lane = row needs two round
         // trips of sixteen (the scan is a chain of L1 / L2 latencies: 2.7 k cycles per scan at config 4, 14 % of its job)
-#ifndef OSOT_X_NO_QUAD_SCAN
-        constexpr bool kQuadScan = (NP == 32);
-#else
-        constexpr bool kQuadScan = false;
-#endif
-        const bool quad_scan = kQuadScan && n_gen > 0 && n_gen <= 16;
+        const bool quad_scan = NP == 32 && n_gen > 0 && n_gen <= 16;
         if (quad_scan) {
             const int lane = WaveCtx<NP>::lane_of(c, h);
             const int gi = lane >> 2, part = lane & 3;

@@ -33,6 +33,18 @@ struct TeamTurns {
 };
 }  // namespace
 
+// The active-set tolerances the wide route was compiled with, by unqualified name from inside namespace big -- what the solver's own code
+// sees: a private copy re-introduced in osot_qp_big.h would shadow the shared header's (osot_qp_tol.h) here exactly as it would there.
+namespace osot { namespace big {
+static void tolerances_seen(double* out) {
+    out[0] = kViolTol; out[1] = kEqTol; out[2] = kDepTol2; out[3] = kDepFloor2; out[4] = kRatioTol; out[5] = kSlackTol;
+    out[6] = kSlackCap; out[7] = kSpanAccept; out[8] = kRefineFloor; out[9] = (double)kRefineMax; out[10] = kInfty;
+}
+} }
+// out[11]: violation, equality, dependence, dependence floor, ratio, slack (relative), slack cap, span accept, refine floor, refinements, infinity
+extern "C" __attribute__((visibility("default")))
+void wide_host_tolerances(double* out) { osot::big::tolerances_seen(out); }
+
 // qb: host pointers, as osot_ihqp_solve takes device pointers.  task_active: [OSOT_MAX_LEVELS * OSOT_MAX_TASKS] or null.
 // nthreads = 1: the team of one; > 1: the turn-taking team with thread 0 first (t0_last = 0) or last (t0_last = 1).
 extern "C" __attribute__((visibility("default")))

@@ -582,7 +582,7 @@ def big_host_solve(H, g, A, lA, uA, l, u, eps_abs, max_iter=0):
     global _big
     if _big is None:
         so = os.path.join(ROOT, "tests", "emu", "libosot_big_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", "osot_qp_big.h"), os.path.join(ROOT, "tests", "emu", "big_host.cpp")]
+        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_qp_big.h", "osot_qp_tol.h")] + [os.path.join(ROOT, "tests", "emu", "big_host.cpp")]
         if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
             subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build.sh")])
         _big = C.CDLL(so)

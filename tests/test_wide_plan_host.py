@@ -21,12 +21,14 @@ def wide_lib():
     global _wide
     if _wide is None:
         so = os.path.join(ROOT, "tests", "emu", "libosot_wide_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_cascade_wide.h", "osot_qp_big.h", "osot_plan_shape.h")] + \
+        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_cascade_wide.h", "osot_qp_big.h", "osot_qp_tol.h", "osot_plan_shape.h")] + \
                [os.path.join(ROOT, "tests", "emu", "cascade_wide_host.cpp")]
         if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
             subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build_wide.sh")])
         _wide = C.CDLL(so)
         _wide.wide_host_ihqp.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.QpBatch), C.c_void_p, C.c_int, C.c_int]
+        _wide.wide_host_tolerances.argtypes = [C.POINTER(C.c_double)]
+        _wide.wide_host_tolerances.restype = None
     return _wide
 
 
@@ -110,6 +112,17 @@ def test_missing_batch_pointer_is_refused(drop):
     asm = pyoracle.assemble(plan, leaf)
     assert wide_host(plan, asm, drop=drop) == abi.ERR_INVALID
     assert (wide_host(plan, asm)[2] == 0).all()      # (the complete batch is solved)
+
+
+def test_wide_route_tolerances_are_the_specified_ones():
+    """the active-set tolerances as the wide route's own code sees them (osot_qp_tol.h, read from inside namespace big) are the literals
+    the rule was specified with -- exact equality: a private copy in osot_qp_big.h with another number would show here"""
+    out = (C.c_double * 11)()
+    wide_lib().wide_host_tolerances(out)
+    names = ("violation", "equality", "dependence", "dependence floor", "ratio", "slack", "slack cap", "span accept",
+             "refine floor", "refinements", "infinity")
+    spec = (1e-11, 1e-9, 1e-24, 1e-13, 1e-14, 1e-6, 1e-5, 1e-8, 1e-9, 2.0, 1e20)
+    assert dict(zip(names, out)) == dict(zip(names, spec))
 
 
 # ---- validator of the workgroup route ------------------------------------------------------------------------------------------

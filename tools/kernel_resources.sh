@@ -1,6 +1,6 @@
 #!/bin/sh
 # developer helper: per-kernel register / scratch / spill figures of the gfx950 build (compiler remarks)
-# usage: tools/kernel_resources.sh [extra hipcc flags, e.g. -DOSOT_X_NO_FUSED_NS]
+# usage: tools/kernel_resources.sh [extra hipcc flags, e.g. -DOSOT_DOT_CH40=20]
 cd "$(dirname "$0")/.."
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -pragma-unroll-threshold=1000000 -Wno-unused-value \
   -Iinclude -Iopensot_amd/csrc --cuda-device-only -c opensot_amd/csrc/osot_mi355x.hip -o /tmp/osot_dev.o "$@" \
