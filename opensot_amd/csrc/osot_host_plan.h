@@ -1,6 +1,7 @@
 // osot_host_plan.h -- host-side translation of the C-ABI plan into kernel arguments (no HIP calls).  What a plan says is read
 // in osot_plan_shape.h; here: the wavefront kernels' memory layout (lane layout, LDS carve-up) and the update kernel's arguments.
 #pragma once
+#include <initializer_list>
 #include "osot_plan_shape.h"
 #include "osot_kernels.h"
 
@@ -56,6 +57,61 @@ inline int make_dev_plan(const osot_plan_desc& p, const unsigned char* level_act
     }
     if (!P.rows_in_global) total += table;
     lds_bytes = (size_t)total * sizeof(double);
+    return OSOT_OK;
+}
+
+// ---- which kernel an iHQP launch of the wavefront route runs ----
+// The decision is a value: choose_kernel_variant computes it from plain facts, osot_mi355x.hip (with_ihqp_kernel) maps it to the
+// instantiation -- for the launch, and over kernel_variants for the dynamic-LDS attribute at creation.
+enum KernelFamily { KERNEL_CASCADE = 0, KERNEL_CYCLE = 1, KERNEL_CONTROL = 2 };   // osot_cascade_kernel / osot_cycle_kernel / osot_control_cycle_kernel
+struct KernelVariant { int family; bool prof, extra, box, roll; };   // the instantiation's PROF / EXTRA / BOX / ROLL (false where the family has no such argument)
+inline bool operator==(const KernelVariant& a, const KernelVariant& b) { return a.family == b.family && a.prof == b.prof && a.extra == b.extra && a.box == b.box && a.roll == b.roll; }
+// (argument lists and defaults as the kernel templates have them after NP)
+constexpr KernelVariant cascade_variant(bool prof, bool extra = false, bool box = false) { return {KERNEL_CASCADE, prof, extra, box, false}; }
+constexpr KernelVariant cycle_variant(bool extra = false, bool box = false) { return {KERNEL_CYCLE, false, extra, box, false}; }
+constexpr KernelVariant control_variant(bool extra = false, bool box = false, bool roll = false) { return {KERNEL_CONTROL, false, extra, box, roll}; }
+
+// every variant of the lane layout T (13, 14 at T = 32): what osot_solver_create prepares.  -> their number
+constexpr int kMaxKernelVariants = 14;
+inline int kernel_variants(int T, KernelVariant* out) {
+    int k = 0;
+    out[k++] = cascade_variant(false); out[k++] = cascade_variant(true);
+    out[k++] = cascade_variant(false, true); out[k++] = cascade_variant(false, false, true);
+    if (T == 32) out[k++] = cascade_variant(true, false, true);   // PROF + BOX: compiled for the headline layout only
+    out[k++] = cycle_variant(); out[k++] = cycle_variant(true); out[k++] = cycle_variant(false, true);
+    for (const bool roll : {false, true}) { out[k++] = control_variant(false, false, roll); out[k++] = control_variant(true, false, roll); out[k++] = control_variant(false, true, roll); }
+    return k;
+}
+
+struct LaunchFacts {
+    int T, nc;                   // padded size (pick_np); constraint rows of the plan as this launch sees it (DevPlan.nc)
+    bool fused, control, roll;   // the update half runs in this launch; so does the producer (osot_control.h); with the rollout loop
+    bool pairs_out, prof;        // the model has collision pairs and the batch asks for their outputs; phase profiling
+    bool plan_extra;             // an inactive task, a dense regularisation task or a level with a dense weight
+    bool hotstart, force_extra, specialise, rows_all_equalities;   // solver state; OSOT_DEBUG_FORCE_EXTRA; osot_solver_set_specialisation; plan_rows_all_equalities
+};
+// -> OSOT_OK and the variant, or the refusal's code and text
+inline int choose_kernel_variant(const LaunchFacts& f, KernelVariant& v, const char** why) {
+    const bool hot_on = f.hotstart && !f.prof;   // (hot start: the EXTRA instantiation carries its code; never together with prof)
+    // (the instrumented instantiation carries no dense-weight / inactive-task code: it would solve another problem)
+    if (f.prof && !f.fused && f.plan_extra) { *why = "phase profiling is not available for plans with dense weights or inactive tasks"; return OSOT_ERR_UNSUPPORTED; }
+    // the instantiation with the dense-weight / inactive-task code only where the plan or the solver state asks for it
+    bool extra = f.plan_extra || hot_on;
+    if (f.force_extra && !f.prof) extra = true;
+    // plans without constraint rows (the bounds are the only inequalities): the BOX instantiation of the 32-column kernels
+    // ... and plans whose rows are all equalities by construction (the feet as TaskToConstraint rows: the reference's COMAN stacks), at
+    // every size -- but only where THIS launch's update half writes lo == up itself (fused): on the solve-only path lo / up are the
+    // caller's arrays, and a row with lo < up would never be scanned by the BOX instantiation
+    bool box = f.specialise && !extra && (f.nc == 0 ? f.T == 32 : (f.fused && f.rows_all_equalities));
+    // the BOX instantiations of osot_control_cycle_kernel are compiled WITHOUT the collision-pair stage of the kinematics (PAIRS = !BOX):
+    // a model with pairs whose batch asks for their outputs takes the general instantiation, whatever the plan's rows (such a
+    // launch used to leave pair_dist / pair_J unwritten without an error)
+    if (f.pairs_out) box = false;
+    if (f.control && (f.prof || !f.fused)) { *why = "the fused control cycle carries no profiling code (use osot_kinematics + osot_cycle)"; return OSOT_ERR_UNSUPPORTED; }
+    if (f.control) v = control_variant(extra, box, f.roll);   // (box only without extra, above)
+    else if (box && (f.T == 32 || !f.prof)) v = f.fused ? cycle_variant(false, true) : cascade_variant(f.prof, false, true);
+    else if (f.fused) v = cycle_variant(extra);
+    else v = cascade_variant(f.prof, extra && !f.prof);
     return OSOT_OK;
 }
 

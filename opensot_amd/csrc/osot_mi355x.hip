@@ -81,6 +81,36 @@ static inline auto by_np(int T, F&& f) {
     return f(std::integral_constant<int, 64>{});
 }
 
+// calls f with the instantiation of variant v (osot_host_plan.h: choose_kernel_variant, kernel_variants) at padded size NP: the one place
+// that names them, for the launch, the dynamic-LDS attribute and the occupancy query alike.  (In the order the code object holds them.)
+template <int NP, class F>
+static int with_ihqp_kernel(const KernelVariant& v, F&& f) {
+    if (v == cascade_variant(false)) return f(osot_cascade_kernel<NP, false>);
+    if (v == cascade_variant(true)) return f(osot_cascade_kernel<NP, true>);
+    if (v == cycle_variant(false)) return f(osot_cycle_kernel<NP, false>);
+    if (v == cycle_variant(true)) return f(osot_cycle_kernel<NP, true>);
+    if (v == cascade_variant(false, true)) return f(osot_cascade_kernel<NP, false, true>);
+    if (v == cascade_variant(false, false, true)) return f(osot_cascade_kernel<NP, false, false, true>);
+    if (v == cycle_variant(false, true)) return f(osot_cycle_kernel<NP, false, true>);
+    if (v == control_variant(false, true)) return f(osot_control_cycle_kernel<NP, false, true>);
+    if (v == control_variant(false, true, true)) return f(osot_control_cycle_kernel<NP, false, true, true>);
+    if (v == control_variant(false, false)) return f(osot_control_cycle_kernel<NP, false, false>);
+    if (v == control_variant(false, false, true)) return f(osot_control_cycle_kernel<NP, false, false, true>);
+    if (v == control_variant(true, false)) return f(osot_control_cycle_kernel<NP, true, false>);
+    if (v == control_variant(true, false, true)) return f(osot_control_cycle_kernel<NP, true, false, true>);
+    if constexpr (NP == 32) if (v == cascade_variant(true, false, true)) return f(osot_cascade_kernel<32, true, false, true>);
+    return fail(OSOT_ERR_UNSUPPORTED, "no kernel instantiation for this variant and lane layout");
+}
+
+// calls f(kernel, its dynamic LDS bytes) with the preparation kernel of an nHQP level of m rows and nf free variables among n
+template <class F>
+static int with_nhqp_prepare_kernel(int m, int nf, int n, F&& f) {
+    if (nhqp_level_is_wide(m, nf)) return f(osot_nhqp_prepare_wide_kernel, nhqp_prepare_wide_lds_bytes(m, n));   // min(rows, free variables) > 32: the full column-side Gram matrix (sym_eig_wide)
+    if (n > 32)     // 33 .. 64 variables: the 64-column kernel (dynamic LDS beyond the 64 KB default: raised once per solver)
+        return m <= 32 ? f(osot_nhqp_prepare64_kernel<32>, nhqp_prepare64_lds_bytes(32, n)) : f(osot_nhqp_prepare64_kernel<64>, nhqp_prepare64_lds_bytes(64, n));
+    return m <= 32 ? f(osot_nhqp_prepare_kernel<32>, (size_t)0) : f(osot_nhqp_prepare_kernel<64>, (size_t)0);
+}
+
 struct osot_solver {
     osot_plan_desc plan;
     int max_batch;
@@ -258,42 +288,22 @@ int osot_solver_create(const osot_plan_desc* plan, int max_batch, int device, os
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
     DevPlan P; int T; size_t lds;
     make_dev_plan(*plan, nullptr, P, T, lds);
+    // every variant a launch can ask for goes through the mapping the launch uses: none is launchable without being prepared
+    const size_t lds_control = lds > control_kin_lds_bytes(T) ? lds : control_kin_lds_bytes(T);
+    KernelVariant all[kMaxKernelVariants];
+    const int n_all = kernel_variants(T, all);
     rc = by_np(T, [&](auto np) {
-        constexpr int NP = decltype(np)::value;
-        int r = ensure_lds(osot_cascade_kernel<NP, false>, lds);
-        if (r == OSOT_OK) r = ensure_lds(osot_cascade_kernel<NP, true>, lds);
-        if (r == OSOT_OK) r = ensure_lds(osot_cycle_kernel<NP, false>, lds);
-        if (r == OSOT_OK) r = ensure_lds(osot_cycle_kernel<NP, true>, lds);
-        if (r == OSOT_OK) r = ensure_lds(osot_cascade_kernel<NP, false, true>, lds);
-        if constexpr (NP != 32) {
-            if (r == OSOT_OK) r = ensure_lds(osot_cascade_kernel<NP, false, false, true>, lds);
-            if (r == OSOT_OK) r = ensure_lds(osot_cycle_kernel<NP, false, true>, lds);
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<NP, false, true>, lds > control_kin_lds_bytes(NP) ? lds : control_kin_lds_bytes(NP));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<NP, false, true, true>, lds > control_kin_lds_bytes(NP) ? lds : control_kin_lds_bytes(NP));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<NP, false, false>, lds > control_kin_lds_bytes(NP) ? lds : control_kin_lds_bytes(NP));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<NP, false, false, true>, lds > control_kin_lds_bytes(NP) ? lds : control_kin_lds_bytes(NP));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<NP, true, false>, lds > control_kin_lds_bytes(NP) ? lds : control_kin_lds_bytes(NP));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<NP, true, false, true>, lds > control_kin_lds_bytes(NP) ? lds : control_kin_lds_bytes(NP));
-        }
-        if constexpr (NP == 32) {
-            if (r == OSOT_OK) r = ensure_lds(osot_cascade_kernel<32, false, false, true>, lds);
-            if (r == OSOT_OK) r = ensure_lds(osot_cycle_kernel<32, false, true>, lds);
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<32, false, true>, lds > control_kin_lds_bytes(32) ? lds : control_kin_lds_bytes(32));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<32, false, true, true>, lds > control_kin_lds_bytes(32) ? lds : control_kin_lds_bytes(32));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<32, false, false>, lds > control_kin_lds_bytes(32) ? lds : control_kin_lds_bytes(32));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<32, false, false, true>, lds > control_kin_lds_bytes(32) ? lds : control_kin_lds_bytes(32));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<32, true, false>, lds > control_kin_lds_bytes(32) ? lds : control_kin_lds_bytes(32));
-            if (r == OSOT_OK) r = ensure_lds(osot_control_cycle_kernel<32, true, false, true>, lds > control_kin_lds_bytes(32) ? lds : control_kin_lds_bytes(32));
-            if (r == OSOT_OK) r = ensure_lds(osot_cascade_kernel<32, true, false, true>, lds);
-        }
+        int r = OSOT_OK;
+        for (int i = 0; i < n_all && r == OSOT_OK; ++i)
+            r = with_ihqp_kernel<decltype(np)::value>(all[i], [&](auto kernel) { return ensure_lds(kernel, all[i].family == KERNEL_CONTROL ? lds_control : lds); });
         return r;
     });
     if (rc != OSOT_OK) return rc;
     osot_solver* s = solver_new(*plan, max_batch, device);
     {   // resident workgroups: what the longest-first dispatch order is planned for (order_body)
         int per_cu = 0, cus = 0;
-        hipError_t e1 = by_np(T, [&](auto np) {
-            return hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_cycle_kernel<decltype(np)::value, false>, 64, lds);
+        const int e1 = by_np(T, [&](auto np) {
+            return with_ihqp_kernel<decltype(np)::value>(cycle_variant(), [&](auto kernel) { return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds); });
         });
         hipError_t e2 = hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device);
         s->slots = (e1 == hipSuccess && e2 == hipSuccess && per_cu > 0 && cus > 0) ? per_cu * cus : 2048;
@@ -492,10 +502,9 @@ int osot_nhqp_solve(osot_solver* s, const osot_qp_batch* b, const osot_nhqp_opti
     if (pl.n > 32) {    // the 64-column preparation kernels' dynamic LDS, once per solver and with its error reported (a
                         // failed attribute call used to skip the launch silently and the solve went on with a stale workspace)
         if (!s->nhqp_lds_ready) {
-            int r = ensure_lds(osot_nhqp_prepare64_kernel<32>, nhqp_prepare64_lds_bytes(32, pl.n));
-            if (r == OSOT_OK) r = ensure_lds(osot_nhqp_prepare64_kernel<64>, nhqp_prepare64_lds_bytes(64, pl.n));
-            if (r == OSOT_OK) r = ensure_lds(osot_nhqp_prepare_wide_kernel, nhqp_prepare_wide_lds_bytes(64, pl.n));
-            if (r != OSOT_OK) return r;
+            const int m_nf[3][2] = {{32, 32}, {64, 32}, {64, 64}};   // the 64-column kernel of either row count and the wide kernel, at their largest
+            for (const auto& c : m_nf)
+                if (const int r = with_nhqp_prepare_kernel(c[0], c[1], pl.n, [](auto kernel, size_t lds) { return ensure_lds(kernel, lds); })) return r;
             s->nhqp_lds_ready = true;
         }
     }
@@ -504,14 +513,7 @@ int osot_nhqp_solve(osot_solver* s, const osot_qp_batch* b, const osot_nhqp_opti
     const char* why = "";
     int rc = nhqp_run(pl, b, opt, s->nhqp,
         [&](const DevNhqp& Q) {
-            if (nhqp_level_is_wide(Q.m, Q.nf))      // min(rows, free variables) > 32: the full column-side Gram matrix (sym_eig_wide)
-                hipLaunchKernelGGL(osot_nhqp_prepare_wide_kernel, dim3(grid), dim3(64), nhqp_prepare_wide_lds_bytes(Q.m, Q.n), st, Q);
-            else if (Q.n > 32) {     // 33 .. 64 variables: the 64-column kernel (dynamic LDS beyond the 64 KB default: raised once, below)
-                if (Q.m <= 32) hipLaunchKernelGGL(osot_nhqp_prepare64_kernel<32>, dim3(grid), dim3(64), nhqp_prepare64_lds_bytes(32, Q.n), st, Q);
-                else hipLaunchKernelGGL(osot_nhqp_prepare64_kernel<64>, dim3(grid), dim3(64), nhqp_prepare64_lds_bytes(64, Q.n), st, Q);
-            }
-            else if (Q.m <= 32) hipLaunchKernelGGL(osot_nhqp_prepare_kernel<32>, dim3(grid), dim3(64), 0, st, Q);
-            else hipLaunchKernelGGL(osot_nhqp_prepare_kernel<64>, dim3(grid), dim3(64), 0, st, Q);
+            with_nhqp_prepare_kernel(Q.m, Q.nf, Q.n, [&](auto kernel, size_t lds) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, st, Q); return 0; });
         },
         [&](int B, int n, int nc, const double* H, const double* g, const double* A, const double* lA, const double* uA,
             const double* l, const double* u, double eps, double* x, int* status, int* iters) {
@@ -547,14 +549,7 @@ int osot_solver_resident_waves_nhqp(osot_solver* s, const osot_nhqp_options* opt
     for (int k = 0; k < pl.n_levels; ++k) {
         int m, ma; plan_level_rows(&pl, k, &m, &ma);
         int per_cu = 0;
-        hipError_t e;
-        if (nhqp_level_is_wide(m, fv[k])) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_nhqp_prepare_wide_kernel, 64, nhqp_prepare_wide_lds_bytes(m, pl.n));
-        else if (pl.n > 32) {
-            if (m <= 32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_nhqp_prepare64_kernel<32>, 64, nhqp_prepare64_lds_bytes(32, pl.n));
-            else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_nhqp_prepare64_kernel<64>, 64, nhqp_prepare64_lds_bytes(64, pl.n));
-        }
-        else if (m <= 32) e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_nhqp_prepare_kernel<32>, 64, 0);
-        else e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_nhqp_prepare_kernel<64>, 64, 0);
+        const int e = with_nhqp_prepare_kernel(m, fv[k], pl.n, [&](auto kernel, size_t lds) { return (int)hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 64, lds); });
         if (e != hipSuccess || per_cu < 1) return fail(OSOT_ERR_HIP, "occupancy query of a preparation kernel failed");
         if (per_cu * cus < least) least = per_cu * cus;
     }
@@ -656,6 +651,14 @@ static int wide_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
     return OSOT_OK;
 }
 
+// hipLaunchKernelGGL of the kernel that with_ihqp_kernel hands over, with its family's argument list
+struct IhqpLaunch {
+    unsigned grid; size_t lds; hipStream_t st; const DevPlan& P; const DevBatch& D; const DevUpdate* fused; const DevControl* control;
+    int operator()(void (*k)(DevPlan, DevBatch)) const { hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, P, D); return OSOT_OK; }
+    int operator()(void (*k)(DevUpdate, DevPlan, DevBatch)) const { hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, *fused, P, D); return OSOT_OK; }
+    int operator()(void (*k)(DevUpdate, DevPlan, DevBatch, DevControl)) const { hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, *fused, P, D, *control); return OSOT_OK; }
+};
+
 static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control) {
     if (!s || !b) return fail(OSOT_ERR_INVALID, "null solver/batch");
     if (b->B < 0 || b->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
@@ -690,83 +693,21 @@ static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
         D.slots = s->slots;
     }
     const unsigned grid = (unsigned)b->B + (D.order_next ? 1u : 0u);   // (+ the order workgroup, block 0)
-    // the instantiation with the dense-weight / inactive-task code only where the plan or the solver state asks for it
-    bool extra = s->any_inactive || (pl.has_regularisation && pl.regularisation_dense);
-    for (int k = 0; k < pl.n_levels; ++k) extra = extra || (s->h_uplan.dense_level[k] != 0);
-    if (prof && !fused && extra)   // (the instrumented instantiation carries no dense-weight / inactive-task code: it would
-        return fail(OSOT_ERR_UNSUPPORTED, "phase profiling is not available for plans with dense weights or inactive tasks");   // solve another problem)
-    extra = extra || (D.hot != nullptr);
-    {   // developer knob: the EXTRA instantiation for every launch (A/B of the two register allocations)
-        static const char* force = getenv("OSOT_DEBUG_FORCE_EXTRA");
-        if (force && force[0] == '1' && !prof) extra = true;
-    }   // (hot start: the EXTRA instantiation carries its code; never together with prof, see D.hot)
-    // plans without constraint rows (the bounds are the only inequalities): the BOX instantiation of the 32-column kernels
-    // ... and plans whose rows are all equalities by construction (the feet as TaskToConstraint rows: the reference's COMAN stacks), at
-    // every size -- but only where THIS launch's update half writes lo == up itself (fused): on the solve-only path lo / up are the
-    // caller's arrays, and a row with lo < up would never be scanned by the BOX instantiation
-    bool box = s->specialise && !extra && (P.nc == 0 ? T == 32 : (fused != nullptr && plan_rows_all_equalities(pl)));
-    // the BOX instantiations of osot_control_cycle_kernel are compiled WITHOUT the collision-pair stage of the kinematics (PAIRS = !BOX):
-    // a model with pairs whose batch asks for their outputs takes the general instantiation, whatever the plan's rows (such a
-    // launch used to leave pair_dist / pair_J unwritten without an error)
-    if (control && control->K_pairs > 0 && (control->Bt.pair_dist || control->Bt.pair_J)) box = false;
-    if (control && (prof || !fused))
-        return fail(OSOT_ERR_UNSUPPORTED, "the fused control cycle carries no profiling code (use osot_kinematics + osot_cycle)");
+    static const char* force = getenv("OSOT_DEBUG_FORCE_EXTRA");   // developer knob: the EXTRA instantiation for every launch (A/B of the two register allocations)
+    LaunchFacts facts;
+    facts.T = T; facts.nc = P.nc; facts.fused = fused != nullptr; facts.control = control != nullptr; facts.prof = prof != nullptr;
+    facts.roll = control && (control->steps > 1 || control->dq_steps || control->status_steps);
+    facts.pairs_out = control && control->K_pairs > 0 && (control->Bt.pair_dist || control->Bt.pair_J);
+    facts.plan_extra = s->any_inactive || (pl.has_regularisation && pl.regularisation_dense);
+    for (int k = 0; k < pl.n_levels; ++k) facts.plan_extra = facts.plan_extra || (s->h_uplan.dense_level[k] != 0);
+    facts.hotstart = s->hotstart != 0; facts.force_extra = force && force[0] == '1'; facts.specialise = s->specialise != 0;
+    facts.rows_all_equalities = plan_rows_all_equalities(pl);
+    KernelVariant v;
+    if (const int r = choose_kernel_variant(facts, v, &why)) return fail(r, why);
     TimedLaunch tl;   // (after EVERY early return: nothing is taken from the pool for a launch that does not happen)
     if (int r = timed_begin(s, st, tl)) return r;
-    const bool roll = control && (control->steps > 1 || control->dq_steps || control->status_steps);
-    by_np(T, [&](auto np) {
-        constexpr int NP = decltype(np)::value;
-        if constexpr (NP == 32) {
-            if (control && roll) {
-                if (box) hipLaunchKernelGGL((osot_control_cycle_kernel<32, false, true, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else if (extra) hipLaunchKernelGGL((osot_control_cycle_kernel<32, true, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else hipLaunchKernelGGL((osot_control_cycle_kernel<32, false, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                return 0;
-            }
-            if (control) {
-                if (box) hipLaunchKernelGGL((osot_control_cycle_kernel<32, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else if (extra) hipLaunchKernelGGL((osot_control_cycle_kernel<32, true, false>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else hipLaunchKernelGGL((osot_control_cycle_kernel<32, false, false>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                return 0;
-            }
-            if (box) {
-                if (fused) hipLaunchKernelGGL((osot_cycle_kernel<32, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D);
-                else if (prof) hipLaunchKernelGGL((osot_cascade_kernel<32, true, false, true>), dim3(grid), dim3(64), lds, st, P, D);
-                else hipLaunchKernelGGL((osot_cascade_kernel<32, false, false, true>), dim3(grid), dim3(64), lds, st, P, D);
-                return 0;
-            }
-        }
-        if constexpr (NP != 32) {
-            if (control && roll) {
-                if (box) hipLaunchKernelGGL((osot_control_cycle_kernel<NP, false, true, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else if (extra) hipLaunchKernelGGL((osot_control_cycle_kernel<NP, true, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else hipLaunchKernelGGL((osot_control_cycle_kernel<NP, false, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                return 0;
-            }
-            if (control) {
-                if (box) hipLaunchKernelGGL((osot_control_cycle_kernel<NP, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else if (extra) hipLaunchKernelGGL((osot_control_cycle_kernel<NP, true, false>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                else hipLaunchKernelGGL((osot_control_cycle_kernel<NP, false, false>), dim3(grid), dim3(64), lds, st, *fused, P, D, *control);
-                return 0;
-            }
-            if (box && !prof) {
-                if (fused) hipLaunchKernelGGL((osot_cycle_kernel<NP, false, true>), dim3(grid), dim3(64), lds, st, *fused, P, D);
-                else hipLaunchKernelGGL((osot_cascade_kernel<NP, false, false, true>), dim3(grid), dim3(64), lds, st, P, D);
-                return 0;
-            }
-        }
-        if (fused) {
-            if (extra) hipLaunchKernelGGL((osot_cycle_kernel<NP, true>), dim3(grid), dim3(64), lds, st, *fused, P, D);
-            else hipLaunchKernelGGL((osot_cycle_kernel<NP, false>), dim3(grid), dim3(64), lds, st, *fused, P, D);
-        } else if (extra && !prof) {
-            hipLaunchKernelGGL((osot_cascade_kernel<NP, false, true>), dim3(grid), dim3(64), lds, st, P, D);
-        } else if (prof) {
-            hipLaunchKernelGGL((osot_cascade_kernel<NP, true>), dim3(grid), dim3(64), lds, st, P, D);
-        } else {
-            hipLaunchKernelGGL((osot_cascade_kernel<NP, false>), dim3(grid), dim3(64), lds, st, P, D);
-        }
-        return 0;
-    });
+    const IhqpLaunch launch{grid, lds, st, P, D, fused, control};
+    if (const int r = by_np(T, [&](auto np) { return with_ihqp_kernel<decltype(np)::value>(v, launch); })) return r;
     HIP_TRY(hipGetLastError());
     if (int r = timed_end(s, st, tl)) return r;
     if (s->schedule == 1) {   // this launch's order workgroup has written the order for the next solve of a batch of this size
@@ -794,16 +735,15 @@ int osot_stack_update(osot_solver* s, const osot_leaf_batch* leaf, const osot_as
     return OSOT_OK;
 }
 
-static int qp_solve_batch_impl(int B, int n, int nc, const double* H, const double* g, const double* A,
-                               const double* lA, const double* uA, const double* l, const double* u,
-                               double eps_abs, int max_iter, double* x, int* status, int* iterations,
-                               void* hip_stream, int* hot);
-
-int osot_qp_solve_batch(int B, int n, int nc, const double* H, const double* g, const double* A,
-                        const double* lA, const double* uA, const double* l, const double* u,
-                        double eps_abs, int max_iter, double* x, int* status, int* iterations,
-                        void* hip_stream) {
-    return qp_solve_batch_impl(B, n, nc, H, g, A, lA, uA, l, u, eps_abs, max_iter, x, status, iterations, hip_stream, nullptr);
+// the argument checks of the explicit-QP entries (n_max: the entry's own size limit); an empty batch passes whatever its pointers
+static int qp_args_check(int B, int n, int n_max, int nc, const double* H, const double* g, const double* A, const double* lA,
+                         const double* uA, const double* l, const double* u, const double* x, const int* status) {
+    if (B < 0 || n < 1 || n > n_max || nc < 0) return fail(OSOT_ERR_INVALID, "bad sizes");
+    if (B == 0) return OSOT_OK;
+    if (!H || !g || !x || !status) return fail(OSOT_ERR_INVALID, "null H/g/x/status");
+    if (nc > 0 && (!A || !lA || !uA)) return fail(OSOT_ERR_INVALID, "nc > 0 but A/lA/uA is null");
+    if ((l == nullptr) != (u == nullptr)) return fail(OSOT_ERR_INVALID, "l and u must both be given or both be null");
+    return OSOT_OK;
 }
 
 // hot: [B][32 or 64] device ints (see DevQP.hot) or null
@@ -811,11 +751,8 @@ static int qp_solve_batch_impl(int B, int n, int nc, const double* H, const doub
                                const double* lA, const double* uA, const double* l, const double* u,
                                double eps_abs, int max_iter, double* x, int* status, int* iterations,
                                void* hip_stream, int* hot) {
-    if (B < 0 || n < 1 || n > OSOT_MAX_QP_VARS || nc < 0) return fail(OSOT_ERR_INVALID, "bad sizes");
+    if (const int r = qp_args_check(B, n, OSOT_MAX_QP_VARS, nc, H, g, A, lA, uA, l, u, x, status)) return r;
     if (B == 0) return OSOT_OK;
-    if (!H || !g || !x || !status) return fail(OSOT_ERR_INVALID, "null H/g/x/status");
-    if (nc > 0 && (!A || !lA || !uA)) return fail(OSOT_ERR_INVALID, "nc > 0 but A/lA/uA is null");
-    if ((l == nullptr) != (u == nullptr)) return fail(OSOT_ERR_INVALID, "l and u must both be given or both be null");
     if (n > OSOT_MAX_VARS) {
         // wider than a wavefront (65 .. 128 variables): one 256-thread workgroup per QP (osot_qp_big.h).  Cold start (the hot-start
         // record of the plugin route is not used), stream-ordered workspace: not for HIP graph capture.
@@ -854,31 +791,29 @@ static int qp_solve_batch_impl(int B, int n, int nc, const double* H, const doub
     const unsigned grid = (unsigned)B;
     const int rc = by_np(T, [&](auto np) -> int {
         constexpr int NP = decltype(np)::value;
-        if (hot) {
-            const int r = ensure_lds(osot_qp_kernel<NP, true>, lds);
-            if (r != OSOT_OK) return r;
-            hipLaunchKernelGGL((osot_qp_kernel<NP, true>), dim3(grid), dim3(64), lds, (hipStream_t)hip_stream, Q);
-        } else {
-            const int r = ensure_lds(osot_qp_kernel<NP, false>, lds);
-            if (r != OSOT_OK) return r;
-            hipLaunchKernelGGL((osot_qp_kernel<NP, false>), dim3(grid), dim3(64), lds, (hipStream_t)hip_stream, Q);
-        }
-        return OSOT_OK;
+        const auto kernel = hot ? osot_qp_kernel<NP, true> : osot_qp_kernel<NP, false>;
+        const int r = ensure_lds(kernel, lds);
+        if (r == OSOT_OK) hipLaunchKernelGGL(kernel, dim3(grid), dim3(64), lds, (hipStream_t)hip_stream, Q);
+        return r;
     });
     if (rc != OSOT_OK) return rc;
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }
 
+int osot_qp_solve_batch(int B, int n, int nc, const double* H, const double* g, const double* A,
+                        const double* lA, const double* uA, const double* l, const double* u,
+                        double eps_abs, int max_iter, double* x, int* status, int* iterations,
+                        void* hip_stream) {
+    return qp_solve_batch_impl(B, n, nc, H, g, A, lA, uA, l, u, eps_abs, max_iter, x, status, iterations, hip_stream, nullptr);
+}
+
 int osot_qp_solve_batch_admm_warm(int B, int n, int nc, const double* H, const double* g, const double* A,
                                   const double* lA, const double* uA, const double* l, const double* u,
                                   double eps_reg, const osot_admm_options* opt, double* warm_x, double* warm_y, double* warm_rho,
                                   double* x, int* status, int* iterations, void* hip_stream) {
-    if (B < 0 || n < 1 || n > OSOT_MAX_VARS || nc < 0) return fail(OSOT_ERR_INVALID, "bad sizes");
+    if (const int r = qp_args_check(B, n, OSOT_MAX_VARS, nc, H, g, A, lA, uA, l, u, x, status)) return r;
     if (B == 0) return OSOT_OK;
-    if (!H || !g || !x || !status) return fail(OSOT_ERR_INVALID, "null H/g/x/status");
-    if (nc > 0 && (!A || !lA || !uA)) return fail(OSOT_ERR_INVALID, "nc > 0 but A/lA/uA is null");
-    if ((l == nullptr) != (u == nullptr)) return fail(OSOT_ERR_INVALID, "l and u must both be given or both be null");
     const bool has_y = (nc + (l ? n : 0)) > 0;
     if ((warm_x == nullptr) != (warm_rho == nullptr) || (warm_x && has_y && !warm_y) || (!warm_x && warm_y))
         return fail(OSOT_ERR_INVALID, "warm_x, warm_y and warm_rho must be given together (or all be null)");

@@ -51,6 +51,29 @@ extern "C" __attribute__((visibility("default"))) int emu_ihqp_solve(const osot_
     return OSOT_OK;
 }
 
+// the launch layer's choice of kernel variant (osot_host_plan.h), for tests/test_launch_variant_host.py.  facts: T, nc, then fused, control,
+// roll, pairs_out, prof, plan_extra, hotstart, force_extra, specialise, rows_all_equalities; variant: family, prof, extra, box, roll
+extern "C" __attribute__((visibility("default"))) int emu_choose_kernel_variant(const int* facts, int* variant, const char** why) {
+    LaunchFacts f;
+    f.T = facts[0]; f.nc = facts[1]; f.fused = facts[2]; f.control = facts[3]; f.roll = facts[4]; f.pairs_out = facts[5]; f.prof = facts[6];
+    f.plan_extra = facts[7]; f.hotstart = facts[8]; f.force_extra = facts[9]; f.specialise = facts[10]; f.rows_all_equalities = facts[11];
+    KernelVariant v = {-1, false, false, false, false};
+    *why = "";
+    const int rc = choose_kernel_variant(f, v, why);
+    variant[0] = v.family; variant[1] = v.prof; variant[2] = v.extra; variant[3] = v.box; variant[4] = v.roll;
+    return rc;
+}
+// variants: [kMaxKernelVariants][5] as above -> how many the layout T has
+extern "C" __attribute__((visibility("default"))) int emu_kernel_variants(int T, int* variants) {
+    KernelVariant all[kMaxKernelVariants];
+    const int n = kernel_variants(T, all);
+    for (int i = 0; i < n; ++i) {
+        int* o = variants + 5 * i;
+        o[0] = all[i].family; o[1] = all[i].prof; o[2] = all[i].extra; o[3] = all[i].box; o[4] = all[i].roll;
+    }
+    return n;
+}
+
 extern "C" __attribute__((visibility("default"))) int emu_qp_solve_batch(int B, int n, int nc, const double* H, const double* g, const double* A,
                                   const double* lA, const double* uA, const double* l, const double* u,
                                   double eps_abs, int max_iter, double* x, int* status, int* iterations) {
