@@ -43,7 +43,8 @@ extern "C" {
 #define OSOT_MAX_BAND_ROWS 6  /* rows of a task used as a constraint (TaskToConstraint error band) */
 #define OSOT_MAX_VARS 64      /* one lane per variable        */
 #define OSOT_MAX_QP_VARS 128  /* the explicit-QP surface (osot_qp_solve_batch, osot_backend_*): 65 .. 128 variables run one
-                                 256-thread workgroup per QP instead of one wavefront (round 6; cold start, no graph capture);
+                                 256-thread workgroup per QP instead of one wavefront (round 6; no graph capture; hot start through
+                                 osot_qp_solve_batch_hot only -- osot_backend_solve starts cold above OSOT_MAX_VARS);
                                  plans: osot_solver_create (the wavefront route) stays at OSOT_MAX_VARS, osot_solver_create_wide
                                  takes up to OSOT_MAX_QP_VARS; nHQP / eHQP and the ADMM kernel stay at OSOT_MAX_VARS */
 
@@ -500,12 +501,36 @@ int osot_backend_get_num_constraints(osot_backend* be, int* nc);
  * n <= OSOT_MAX_QP_VARS (128).  Problems of 65 .. 128 variables -- wider than a wavefront: include/OpenSoT/Task.h:47-565 has no limit, a
  * 45-DoF robot or a floating-base inverse-dynamics stack with five contacts is such a problem -- run one 256-thread WORKGROUP per QP
  * (opensot_amd/csrc/osot_qp_big.h: the same dual active-set method; J in a stream-ordered device workspace of 2 n^2 doubles per
- * resident QP, R and the vectors in LDS; nc <= 2048).  That path starts cold on every call (osot_backend_solve included: the plugin's
- * hot-start record is for n <= 64) and allocates with hipMallocAsync on the caller's stream: do not capture it into a HIP graph. */
+ * resident QP, R and the vectors in LDS; nc <= 2048).  Through this entry that path starts cold on every call (so does
+ * osot_backend_solve: the plugin's hot-start record is for n <= 64; osot_qp_solve_batch_hot carries working sets at every size) and
+ * allocates with hipMallocAsync on the caller's stream: do not capture it into a HIP graph. */
 int osot_qp_solve_batch(int B, int n, int nc, const double* H, const double* g, const double* A,
                         const double* lA, const double* uA, const double* l, const double* u,
                         double eps_abs, int max_iter, double* x, int* status, int* iterations,
                         void* hip_stream);
+
+/* HOT START for the call above: the working sets carried from call to call, as the reference's qpOASES back-end hot-starts every
+ * solve from the previous one's (QPOasesBackEnd.cpp:258-285 -> SQProblem.cpp:149-193).  The state is a device array owned by the
+ * caller, hot_state [B][ints] with ints from osot_qp_hot_state_ints(n) (32 for n <= 32, 64 for n <= 64, 128 for n <= 128;
+ * OSOT_ERR_INVALID outside 1 .. OSOT_MAX_QP_VARS or with a null out pointer; host only, no GPU needed).  Row i belongs to INSTANCE i
+ * of the call.  The kernel reads it before the solve and rewrites it after.  Entry -1 means "none": a state filled with 0xff bytes
+ * (hipMemset) is a cold start: the same iterations as osot_qp_solve_batch (above 64 variables the same bits: the hot kernel runs the
+ * cold kernel's instructions until it finds an entry).  Every other value is an opaque constraint code
+ * of THIS library for THIS shape (n, nc): reset the state to 0xff when n or nc changes, and do not carry it to another version of the
+ * library.  Whatever the state holds, the answer is the cold one up to round-off (the minimiser is unique; entries that name no
+ * constraint of the problem, a constraint already in the set, an equality row, a side without a finite bound or a dependent normal
+ * are skipped, stale ones are taken out again): what changes is the iteration count.
+ * What a call leaves behind: an instance that ends OSOT_STATUS_SOLVED leaves the inequality part of its final working set compacted
+ * to the front and -1 behind.  n > 64: an instance that does not end SOLVED leaves all -1.  n <= 64: an instance that fails in the
+ * inequality loop (INFEASIBLE, MAX_ITER) leaves all -1; one that is refused before it (NOT_PD, or an inconsistent dependent equality
+ * row: INFEASIBLE from the equality phase) leaves its row as it was -- harmless, see above.
+ * hot_state == NULL is exactly osot_qp_solve_batch.  Same argument checks, same workspace rule above 64 variables (hipMallocAsync on
+ * the caller's stream: not for HIP graph capture). */
+int osot_qp_hot_state_ints(int n, int* ints);
+int osot_qp_solve_batch_hot(int B, int n, int nc, const double* H, const double* g, const double* A,
+                            const double* lA, const double* uA, const double* l, const double* u,
+                            double eps_abs, int max_iter, double* x, int* status, int* iterations,
+                            int* hot_state, void* hip_stream);
 
 /* The same call through the SECOND back-end: an OSQP-convention ADMM solver -- the problem as
  * src/solvers/OSQPBackEnd.cpp poses it (P = H + eps I, one constraint matrix [A; I] with piled bounds, eps_abs = eps_rel =

@@ -167,6 +167,7 @@ SYMBOLS = [
     "osot_backend_set_eps_regularisation", "osot_backend_get_eps_regularisation",
     "osot_backend_get_num_variables", "osot_backend_get_num_constraints",
     "osot_qp_solve_batch", "osot_qp_solve_batch_admm", "osot_qp_solve_batch_admm_warm",
+    "osot_qp_hot_state_ints", "osot_qp_solve_batch_hot",
     "osot_comm_unique_id", "osot_comm_create", "osot_comm_destroy", "osot_allgather_dq", "osot_abi_layout",
 ]
 
@@ -254,6 +255,9 @@ def lib():
     L.osot_backend_get_num_constraints.argtypes = [vp, ip]
     L.osot_qp_solve_batch.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                       C.c_double, C.c_int, vp, vp, vp, vp]
+    L.osot_qp_hot_state_ints.argtypes = [C.c_int, ip]
+    L.osot_qp_solve_batch_hot.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
+                                          C.c_double, C.c_int, vp, vp, vp, vp, vp]
     L.osot_qp_solve_batch_admm.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                            C.c_double, C.c_int, vp, vp, vp, vp]
     L.osot_qp_solve_batch_admm_warm.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,

@@ -746,7 +746,7 @@ static int qp_args_check(int B, int n, int n_max, int nc, const double* H, const
     return OSOT_OK;
 }
 
-// hot: [B][32 or 64] device ints (see DevQP.hot) or null
+// hot: [B][osot_qp_hot_state_ints(n)] device ints (n <= 64: DevQP.hot; above: DevQPBigHot.hot) or null
 static int qp_solve_batch_impl(int B, int n, int nc, const double* H, const double* g, const double* A,
                                const double* lA, const double* uA, const double* l, const double* u,
                                double eps_abs, int max_iter, double* x, int* status, int* iterations,
@@ -754,8 +754,8 @@ static int qp_solve_batch_impl(int B, int n, int nc, const double* H, const doub
     if (const int r = qp_args_check(B, n, OSOT_MAX_QP_VARS, nc, H, g, A, lA, uA, l, u, x, status)) return r;
     if (B == 0) return OSOT_OK;
     if (n > OSOT_MAX_VARS) {
-        // wider than a wavefront (65 .. 128 variables): one 256-thread workgroup per QP (osot_qp_big.h).  Cold start (the hot-start
-        // record of the plugin route is not used), stream-ordered workspace: not for HIP graph capture.
+        // wider than a wavefront (65 .. 128 variables): one 256-thread workgroup per QP (osot_qp_big.h).  hot: the instantiation
+        // that carries the hot-start code, else the plain one.  Stream-ordered workspace: not for HIP graph capture.
         if (nc > big::kMaxRows) return fail(OSOT_ERR_UNSUPPORTED, "more than 2048 constraint rows with more than 64 variables");
         DevQPBig Q;
         std::memset(&Q, 0, sizeof(Q));
@@ -765,14 +765,15 @@ static int qp_solve_batch_impl(int B, int n, int nc, const double* H, const doub
         Q.H = H; Q.g = g; Q.A = A; Q.lA = lA; Q.uA = uA; Q.l = l; Q.u = u;
         Q.x = x; Q.status = status; Q.iterations = iterations;
         const size_t lds = big::shared_bytes(n, nc);
-        int r = ensure_lds(osot_qp_big_kernel, lds);
+        int r = hot ? ensure_lds(osot_qp_big_hot_kernel, lds) : ensure_lds(osot_qp_big_kernel, lds);
         if (r != OSOT_OK) return r;
         // (workgroups in flight: 30 KB of LDS at n = 70 lets five share a CU, 82 KB at n = 128 one; the workspace is 2 n^2 doubles each)
         const unsigned cap = n <= 96 ? 1024u : 512u;
         const unsigned grid = (unsigned)B < cap ? (unsigned)B : cap;
         const size_t wbytes = (size_t)grid * 2 * (size_t)n * n * sizeof(double);
         HIP_TRY(hipMallocAsync((void**)&Q.work, wbytes, (hipStream_t)hip_stream));
-        hipLaunchKernelGGL(osot_qp_big_kernel, dim3(grid), dim3(256), lds, (hipStream_t)hip_stream, Q);
+        if (hot) hipLaunchKernelGGL(osot_qp_big_hot_kernel, dim3(grid), dim3(256), lds, (hipStream_t)hip_stream, DevQPBigHot{Q, hot});
+        else hipLaunchKernelGGL(osot_qp_big_kernel, dim3(grid), dim3(256), lds, (hipStream_t)hip_stream, Q);
         const hipError_t le = hipGetLastError();
         HIP_TRY(hipFreeAsync(Q.work, (hipStream_t)hip_stream));
         HIP_TRY(le);
@@ -806,6 +807,20 @@ int osot_qp_solve_batch(int B, int n, int nc, const double* H, const double* g, 
                         double eps_abs, int max_iter, double* x, int* status, int* iterations,
                         void* hip_stream) {
     return qp_solve_batch_impl(B, n, nc, H, g, A, lA, uA, l, u, eps_abs, max_iter, x, status, iterations, hip_stream, nullptr);
+}
+
+int osot_qp_hot_state_ints(int n, int* ints) {
+    if (!ints) return fail(OSOT_ERR_INVALID, "null out");
+    if (n < 1 || n > OSOT_MAX_QP_VARS) return fail(OSOT_ERR_INVALID, "n out of range (1..128)");
+    *ints = n <= 32 ? 32 : (n <= OSOT_MAX_VARS ? 64 : big::kHotLen);   // (n <= 64: WaveCtx<NP>::LW of the lane layout pick_np(n) selects)
+    return OSOT_OK;
+}
+
+int osot_qp_solve_batch_hot(int B, int n, int nc, const double* H, const double* g, const double* A,
+                            const double* lA, const double* uA, const double* l, const double* u,
+                            double eps_abs, int max_iter, double* x, int* status, int* iterations,
+                            int* hot_state, void* hip_stream) {
+    return qp_solve_batch_impl(B, n, nc, H, g, A, lA, uA, l, u, eps_abs, max_iter, x, status, iterations, hip_stream, hot_state);
 }
 
 int osot_qp_solve_batch_admm_warm(int B, int n, int nc, const double* H, const double* g, const double* A,
@@ -900,7 +915,8 @@ int backend_run(osot_backend* be) {
     }
     int rc = qp_solve_batch_impl(1, n, nc, dH, dg, nc ? dA : nullptr, nc ? dlA : nullptr, nc ? duA : nullptr,
                                  be->has_bounds ? dl : nullptr, be->has_bounds ? du : nullptr, be->eps_abs, be->max_iterations,
-                                 dx, be->d_status, be->d_status + 1, nullptr, be->d_hot);
+                                 dx, be->d_status, be->d_status + 1, nullptr,
+                                 n > OSOT_MAX_VARS ? nullptr : be->d_hot);   // (above 64 variables the plugin starts cold: its record is 64 codes)
     if (rc != OSOT_OK) return rc;
     int st[2];
     HIP_TRY(hipMemcpy(st, be->d_status, 2 * sizeof(int), hipMemcpyDeviceToHost));

@@ -52,6 +52,11 @@ struct Args {                         // one instance
     bool accept_slack = false;
     double* slack = nullptr;
     double *lmut = nullptr, *umut = nullptr;
+    // hot start (solve<true> only; the cold instantiation reads neither): kHotLen codes in global memory each, hot_code() of the
+    // inequality working set this problem ended with last time, -1 = none.  Both null: cold.  They may be the same array (the list is
+    // read before it is written).  (A cascade would hand in one list per level: the codes are positions in THIS level's rows.)
+    const int* hot_in = nullptr;
+    int* hot_out = nullptr;
 };
 
 // The constraint rows as the solver sees them.  DenseRows: the explicit QP's A [nc][n] with lA <= A x <= uA.  A row source must
@@ -72,7 +77,7 @@ struct DenseRows {
         return acc;
     }
 };
-enum { SI_IQ = 0, SI_ME, SI_IP, SI_SIDE, SI_ACT, SI_L, SI_ST, SI_ITERS, SI_DONE, SI_REFINE, SI_COUNT = 16 };
+enum { SI_IQ = 0, SI_ME, SI_IP, SI_SIDE, SI_ACT, SI_L, SI_ST, SI_ITERS, SI_DONE, SI_REFINE, SI_HOTQ, SI_HOTN, SI_HOTSINCE, SI_HOTADDED, SI_COUNT = 16 };
 enum { SD_T = 0, SD_ND2, SD_DD, SD_ALPHA, SD_BETA, SD_SIP, SD_PIV, SD_BND, SD_SLACK, SD_COUNT = 16 };
 struct Shared {                       // LDS on the device, heap on the host
     double* R;                        // packed upper triangle of the working set's factor: R(i, j) at j (j + 1) / 2 + i, i <= j
@@ -115,10 +120,24 @@ OSOT_BIG_FN int ridx(int i, int j) { return ((j * (j + 1)) >> 1) + i; }
 OSOT_BIG_FN double DenseRows::lo(int r) const { return clamp_inf(lA[r]); }
 OSOT_BIG_FN double DenseRows::up(int r) const { return clamp_inf(uA[r]); }
 
+// ---- hot start: the list of a previous solve's inequality working set (Args::hot_in / hot_out)
+constexpr int kHotLen = kMaxVars;         // entries per list
+// the stale-list guard and the negative-multiplier threshold of the wavefront route, restated (osot_qp_core.h, gi_inequalities: the
+// constants of the same names are local to that function; tests/test_qp_hot_host.py compares the two texts)
+constexpr int kHotBatch = 4;              // the multipliers are looked at after every kHotBatch hot additions ...
+constexpr int kHotAbandon = 3;            // ... and with at least kHotAbandon negative, and a quarter of the additions so far, the rest of the list is not tried
+// (The guard counts negative multipliers only.  An entry that passes the validity checks but whose normal turns out dependent on the
+// set costs one compute_d -- an n^2 pass and three barriers -- and is neither an addition nor an iteration: a foreign list of
+// dependent normals gets up to kHotLen such trips past the guard and past max_iter.  The list's length is the bound.)
+constexpr double kHotDropTol = 1.0e-13;   // a multiplier below -kHotDropTol max|u| is negative (above: round-off of zero)
+// one list entry: constraint code (variable k, or n + row) and side (+1 lower, -1 upper); decoded as code = e >> 1, side from e & 1
+OSOT_BIG_FN int hot_code(int code, int side) { return 2 * code + ((side < 0) ? 1 : 0); }
+
 #define OSOT_BIG_FOR(i, N) for (int i = tm.tid; i < (N); i += tm.nt)
 
 // Team: { int tid, nt; void sync() const; }  -- every thread of the team calls solve() with the same arguments
-template <class Team, class Rows>
+// HOT: the instantiation that carries the hot-start code (Args::hot_in / hot_out); the plain one carries none of it
+template <bool HOT = false, class Team, class Rows>
 OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Rows& rows) {
     const int n = a.n, nc = a.nc;
     const bool t0 = tm.tid == 0;
@@ -136,6 +155,12 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
         const int st = s.si[SI_ST];
         OSOT_BIG_FOR(i, n) a.x[i] = (st == ST_SOLVED) ? s.x[i] : 0.0;
         if (t0) { *a.status = st; if (a.iters) *a.iters = s.si[SI_ITERS]; if (a.slack) *a.slack = fmax(*a.slack, s.sc[SD_SLACK]); }
+        if constexpr (HOT) {           // the inequality part of the working set, compacted to the front, for this problem's next solve
+            if (a.hot_out) {
+                const int me0 = s.si[SI_ME], cnt = (st == ST_SOLVED) ? s.si[SI_IQ] - me0 : 0;
+                OSOT_BIG_FOR(q, kHotLen) a.hot_out[q] = (q < cnt) ? hot_code(s.aset[me0 + q], s.aside[me0 + q]) : -1;
+            }
+        }
         tm.sync();
     };
     // ---- Cholesky of H + eps I, right-looking, in place (lower triangle of L)
@@ -312,6 +337,126 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
     tm.sync();
     const int me = s.si[SI_ME];
 
+    // ---- HOT START (the method of the wavefront route, osot_qp_core.h gi_inequalities, restated for the team; the reference's
+    // qpOASES back-end keeps its working set from one control cycle to the next, QPOasesBackEnd.cpp:258-285).  The constraints of the
+    // list are re-added first, each as if it were an equality: a SIGNED full step onto its boundary, the multipliers updated by the
+    // same dual direction, no scan and no ratio test.  Then every constraint whose multiplier came out negative is taken out again by
+    // the reverse of an addition (x' = x - u_k z, u' = u + u_k r with z, r of its normal against the factors of the set without it):
+    // each removal moves to the minimiser over a subset, f strictly decreases, so the phase ends in an S-pair (x minimises f on the
+    // working set, all multipliers >= 0) -- a valid state of the dual method, which goes on below as from a cold start.  The minimiser
+    // is unique: the answer is the cold one up to round-off, what changes is the number of iterations.  A STALE list must not cost
+    // more than it can save: see kHotBatch / kHotAbandon.  Thread 0 walks the list and takes the scalar decisions;
+    // d, z, the reflection and the rotations are the team's, as in the dual loop.
+    if constexpr (HOT) {
+        if (a.hot_in) {
+            if (t0) { s.si[SI_HOTQ] = 0; s.si[SI_HOTN] = kHotLen; s.si[SI_HOTSINCE] = 0; s.si[SI_HOTADDED] = 0; }
+            // the list comes into LDS in one parallel pass (thread 0 walking it in global memory is a chain of 128 round trips); it
+            // borrows the scan's violation array, which nothing reads before the first scan rewrites it.  What does not fit
+            // (n + nc < 64) thread 0 reads where it is.
+            int* hl = reinterpret_cast<int*>(s.cval);
+            const int nst = (2 * (n + nc) < kHotLen) ? 2 * (n + nc) : kHotLen;
+            OSOT_BIG_FOR(q, nst) hl[q] = a.hot_in[q];
+            // thread 0: largest |u| and the most negative u over the inequality positions; the count of negative ones
+            auto look = [&](int& lmin, int& nneg) {
+                const int iq = s.si[SI_IQ];
+                double umax = 0.0, umin = 0.0;
+                for (int k = me; k < iq; ++k) umax = fmax(umax, fabs(s.u[k]));
+                lmin = -1; nneg = 0;
+                for (int k = me; k < iq; ++k)
+                    if (s.u[k] < -kHotDropTol * umax) { ++nneg; if (s.u[k] < umin) { umin = s.u[k]; lmin = k; } }
+            };
+            for (;;) {                                   // additions
+                tm.sync();                               // (the scalars of the previous entry have been read by everybody)
+                if (t0) {
+                    int q = s.si[SI_HOTQ], hn = s.si[SI_HOTN];
+                    int act = 0;
+                    while (q < hn) {
+                        if (s.si[SI_HOTSINCE] >= kHotBatch) {        // a look in the middle of the list: count, do not remove (a PARTIAL
+                            int lmin, nneg;                          // set can show a negative multiplier that the complete one does not)
+                            look(lmin, nneg);
+                            s.si[SI_HOTSINCE] = 0;
+                            if (nneg >= kHotAbandon && 4 * nneg >= s.si[SI_HOTADDED]) { hn = q; break; }
+                        }
+                        const int enc = (q < nst) ? hl[q] : a.hot_in[q];
+                        ++q;
+                        if (enc < 0) continue;
+                        const int code = enc >> 1, side = (enc & 1) ? -1 : +1;
+                        if (code >= n + nc) continue;                // not a constraint of this problem
+                        double bnd;
+                        if (code < n) {
+                            if (!has_box || s.bstate[code] != 0) continue;               // in the working set already
+                            bnd = (side > 0) ? clamp_inf(a.l[code]) : clamp_inf(a.u[code]);
+                        } else {
+                            if (s.rstate[code - n] != 0) continue;                       // in the set already, or an equality row
+                            bnd = (side > 0) ? rows.lo(code - n) : rows.up(code - n);
+                        }
+                        if ((side > 0) ? !(bnd > -kInfty) : !(bnd < kInfty)) continue;   // no bound on that side
+                        s.si[SI_IP] = code; s.si[SI_SIDE] = side; s.sc[SD_BND] = bnd;
+                        act = 1;
+                        break;
+                    }
+                    s.si[SI_HOTQ] = q; s.si[SI_HOTN] = hn; s.si[SI_ACT] = act;
+                }
+                tm.sync();
+                if (s.si[SI_ACT] == 0) break;
+                const int ip = s.si[SI_IP], side = s.si[SI_SIDE];
+                compute_d(ip, side);
+                if (!(s.sc[SD_ND2] > kDepTol2 * s.sc[SD_DD])) continue;                  // dependent on the set: not taken
+                if (t0) {
+                    const int iq = s.si[SI_IQ];
+                    for (int j = iq - 1; j >= 0; --j) {              // r = R^-1 d1
+                        double acc = s.d[j];
+                        for (int k = j + 1; k < iq; ++k) acc -= Rp[ridx(j, k)] * s.r[k];
+                        s.r[j] = acc / Rp[ridx(j, j)];
+                    }
+                    const double ax = (ip < n) ? s.x[ip] : rows.dot(ip - n, s.x);
+                    const double t = -(side * (ax - s.sc[SD_BND])) / s.sc[SD_ND2];       // onto the boundary, either sign
+                    for (int k = 0; k < iq; ++k) s.u[k] -= t * s.r[k];
+                    s.u[iq] = t;
+                    s.sc[SD_T] = t;
+                    s.si[SI_HOTSINCE] += 1; s.si[SI_HOTADDED] += 1;
+                    s.si[SI_ACT] = (++s.si[SI_ITERS] > a.max_iter) ? 4 : 1;
+                }
+                tm.sync();
+                if (s.si[SI_ACT] == 4) { if (t0) s.si[SI_ST] = ST_MAX_ITER; tm.sync(); finish(); return; }
+                const double t = s.sc[SD_T];
+                OSOT_BIG_FOR(i, n) s.x[i] += t * s.z[i];
+                add_constraint(ip, side);
+            }
+            for (;;) {                                   // removals: the most negative multiplier, while there is one
+                tm.sync();
+                if (t0) {
+                    int lmin = -1, nneg = 0;
+                    if (s.si[SI_HOTADDED] > 0) look(lmin, nneg);
+                    int act = 0;
+                    if (lmin >= 0) {
+                        s.si[SI_L] = lmin; s.si[SI_IP] = s.aset[lmin]; s.si[SI_SIDE] = s.aside[lmin]; s.sc[SD_T] = s.u[lmin];
+                        act = (++s.si[SI_ITERS] > a.max_iter) ? 4 : 2;
+                    }
+                    s.si[SI_ACT] = act;
+                }
+                tm.sync();
+                if (s.si[SI_ACT] == 0) break;
+                if (s.si[SI_ACT] == 4) { if (t0) s.si[SI_ST] = ST_MAX_ITER; tm.sync(); finish(); return; }
+                const int l = s.si[SI_L], ip = s.si[SI_IP], side = s.si[SI_SIDE];
+                const double uk = s.sc[SD_T];
+                drop_constraint(l);
+                compute_d(ip, side);                     // (against the factors of the set without it)
+                if (t0) {
+                    const int iq = s.si[SI_IQ];
+                    for (int j = iq - 1; j >= 0; --j) {
+                        double acc = s.d[j];
+                        for (int k = j + 1; k < iq; ++k) acc -= Rp[ridx(j, k)] * s.r[k];
+                        s.r[j] = acc / Rp[ridx(j, j)];
+                    }
+                    for (int k = 0; k < iq; ++k) s.u[k] += uk * s.r[k];
+                    s.u[iq] = 0.0;
+                }
+                OSOT_BIG_FOR(i, n) s.x[i] -= uk * s.z[i];
+            }
+        }
+    }
+
     // ---- the dual loop
     for (;;) {
         // most violated inactive constraint
@@ -439,8 +584,8 @@ OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s, const Row
     finish();
 }
 // the explicit QP: dense rows A [nc][n]
-template <class Team>
-OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) { solve(tm, a, s, DenseRows{a.A, a.lA, a.uA, a.n}); }
+template <bool HOT = false, class Team>
+OSOT_BIG_FN void solve(const Team& tm, const Args& a, const Shared& s) { solve<HOT>(tm, a, s, DenseRows{a.A, a.lA, a.uA, a.n}); }
 
 }  // namespace big
 
@@ -476,6 +621,35 @@ __global__ void __launch_bounds__(256) osot_qp_big_kernel(const DevQPBig Q) {
         a.x = Q.x + inst * n; a.status = Q.status + inst; a.iters = Q.iterations ? Q.iterations + inst : nullptr;
         a.Lw = slot; a.J = slot + (size_t)n * n;
         big::solve(tm, a, sh);
+        __syncthreads();
+    }
+}
+// the same walk with the working sets carried from call to call (osot_qp_solve_batch_hot): row inst of hot belongs to instance inst of
+// the batch, whichever workgroup solves it; read before the solve, rewritten after it.  (A copy of the walk above, on purpose: with
+// both kernels calling one function template over HOT the cold kernel came out 20 bytes longer and with other SGPR spills than its
+// parent's -- profiles/qp_hot_codegen.txt -- and the cold kernel's code is not to move for a feature it does not run.)
+struct DevQPBigHot {
+    DevQPBig q;
+    int* hot;                         // [B][big::kHotLen]
+};
+__global__ void __launch_bounds__(256) osot_qp_big_hot_kernel(const DevQPBigHot QH) {
+    extern __shared__ __attribute__((aligned(16))) char osot_big_smem[];
+    const DevQPBig& Q = QH.q;
+    const int n = Q.n, nc = Q.nc;
+    const big::Shared sh = big::carve(osot_big_smem, n, nc);
+    const BigTeamDev tm{(int)threadIdx.x, (int)blockDim.x};
+    double* slot = Q.work + (size_t)blockIdx.x * 2 * (size_t)n * n;
+    for (long long inst = blockIdx.x; inst < Q.B; inst += gridDim.x) {
+        big::Args a;
+        a.n = n; a.nc = nc; a.max_iter = Q.max_iter; a.eps = Q.eps_abs;
+        a.H = Q.H + inst * (long long)n * n; a.g = Q.g + inst * n;
+        a.A = nc ? Q.A + inst * (long long)nc * n : nullptr;
+        a.lA = nc ? Q.lA + inst * nc : nullptr; a.uA = nc ? Q.uA + inst * nc : nullptr;
+        a.l = Q.l ? Q.l + inst * n : nullptr; a.u = Q.u ? Q.u + inst * n : nullptr;
+        a.x = Q.x + inst * n; a.status = Q.status + inst; a.iters = Q.iterations ? Q.iterations + inst : nullptr;
+        a.Lw = slot; a.J = slot + (size_t)n * n;
+        a.hot_in = QH.hot + inst * big::kHotLen; a.hot_out = QH.hot + inst * big::kHotLen;
+        big::solve<true>(tm, a, sh);
         __syncthreads();
     }
 }

@@ -46,13 +46,25 @@ def admm_state(B, n, nc, box=True, device=0):
             "rho": torch.zeros((B,), dtype=torch.float64, device=dev)}
 
 
+def qp_hot_state(B, n, device=0):
+    """the hot-start state of the active-set back-end for B QPs of n variables (osot_qp_solve_batch_hot): int32 [B][ints], every
+    entry -1 = "nothing recorded" (a cold start).  Row i is instance i's inequality working set as its last solve left it, in codes
+    that belong to this library and to ONE shape (n, nc): take a fresh state (or fill_(-1)) when the shape changes."""
+    ints = C.c_int(0)
+    abi.check(abi.lib().osot_qp_hot_state_ints(int(n), C.byref(ints)), "osot_qp_hot_state_ints")
+    dev = torch.device("cuda", device) if isinstance(device, int) else device
+    return torch.full((B, ints.value), -1, dtype=torch.int32, device=dev)
+
+
 def qp_solve(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=2e2, be_solver=solver_back_ends.qpOASES,
-             max_iter=0, warm=None, scaling=0):
+             max_iter=0, warm=None, scaling=0, hot=None):
     """B QPs  min 1/2 x'Hx + g'x  s.t.  lA <= A x <= uA,  l <= x <= u  (BackEnd.h:125-150).
     H [B][n][n], g [B][n], A [B][nc][n], lA / uA [B][nc], l / u [B][n] (A.. and l, u optional), float64, on one GPU.
     eps_regularisation is the back-end factory's FACTOR (BackEndFactory.cpp:4-17).
     OSQP back-end only: warm = admm_state(...) carried from call to call (warm start), scaling = Ruiz passes (0 = osqp's 10,
     negative = none).
+    Active-set back-end only: hot = qp_hot_state(B, n) carried from call to call (hot start: every solve begins from the working set
+    the instance's previous solve ended with, as QPOasesBackEnd::solve does; the answer is the cold one up to round-off).
     Returns (x [B][n], status [B] int32 OSOT_STATUS_*, iterations [B] int32), stream-ordered on the current stream."""
     lib = abi.lib()
     if H.dim() != 3 or H.shape[1] != H.shape[2]:
@@ -69,6 +81,8 @@ def qp_solve(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=
     stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
     with torch.cuda.device(dev):
         if be_solver == solver_back_ends.OSQP:
+            if hot is not None:
+                raise ValueError("hot is the active-set back-end's state; the OSQP back-end's warm start is warm = admm_state(...)")
             opt = abi.AdmmOptions()
             opt.max_iter = max_iter
             opt.scaling = scaling
@@ -82,7 +96,17 @@ def qp_solve(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=
                                                         C.c_void_p(iters.data_ptr()), stream), "osot_qp_solve_batch_admm_warm")
         else:
             if warm is not None:
-                raise ValueError("warm is the OSQP back-end's state; the active-set back-end's hot start lives in BatchedStack.set_hotstart")
+                raise ValueError("warm is the OSQP back-end's state; the active-set back-end's hot start is hot = qp_hot_state(...)")
+            if hot is not None:
+                if not isinstance(hot, torch.Tensor) or hot.device != dev:
+                    raise TypeError(f"hot must be a tensor on {dev}, where the problem is")
+                ints = C.c_int(0)
+                abi.check(lib.osot_qp_hot_state_ints(n, C.byref(ints)), "osot_qp_hot_state_ints")
+                ph = _chk(hot, "hot", (B, ints.value), dtype=torch.int32)
+                abi.check(lib.osot_qp_solve_batch_hot(B, n, nc, pH, pg, pA, plA, puA, pl, pu, eps_abs_from_factor(eps_regularisation),
+                                                      max_iter, C.c_void_p(x.data_ptr()), C.c_void_p(status.data_ptr()),
+                                                      C.c_void_p(iters.data_ptr()), ph, stream), "osot_qp_solve_batch_hot")
+                return x, status, iters
             abi.check(lib.osot_qp_solve_batch(B, n, nc, pH, pg, pA, plA, puA, pl, pu, eps_abs_from_factor(eps_regularisation), max_iter,
                                               C.c_void_p(x.data_ptr()), C.c_void_p(status.data_ptr()),
                                               C.c_void_p(iters.data_ptr()), stream), "osot_qp_solve_batch")
