@@ -175,14 +175,26 @@ typedef enum {
                                             pyramid(mu/sqrt2) * wRl' on the force columns, 0 on the torque columns */
     OSOT_ROWS_COP = 11,               /* force::CoP (CoP.cpp:24-69): 4 rows per contact, Ai * Ad (the CoP inside the
                                          rectangle [x_l, x_u] x [y_l, y_u]) */
-    OSOT_ROWS_NORMAL_TORQUE = 12      /* force::NormalTorque (NormalTorque.cpp:5-69): 8 rows per contact, A0 * Ad2 * Ad
+    OSOT_ROWS_NORMAL_TORQUE = 12,     /* force::NormalTorque (NormalTorque.cpp:5-69): 8 rows per contact, A0 * Ad2 * Ad
                                          with mu = the block's mu */
+    /* (13, 14 and 15 are not kinds: both validators refuse them as "unknown row-block kind") */
+    /* velocity::ConvexHull (src/constraints/velocity/ConvexHull.cpp:41-134, src/utils/convex_hull_utils.cpp:142-174): the CoM's
+     * ground projection stays inside the support polygon of the contact points.  rows = P contact points (3 .. 16) = the fixed
+     * number of rows (_C(links_in_contact.size(), 2)); bound_scaling = the safety margin in metres (setSafetyMargin).  Stored
+     * rows, written by every update: the points are taken relative to the CoM and projected on z = 0, their convex hull is built
+     * in fp64 (exact sign tests, no epsilon; duplicates of a lower-indexed point and points on a segment between two others are
+     * no vertices), row r is the edge from the r-th hull vertex IN ORDER OF POINT INDEX to its counter-clockwise successor:
+     * (a, b, c) of getLineCoefficients, C_r = +-(a J_com,x + b J_com,y), up_r = |c| - margin sqrt(a^2 + b^2) (the sign as
+     * getConstraints picks it: c <= 0 keeps (a, b)), lo_r = -1e20.  Rows at or beyond the vertex count: C_r = 0, up_r = 1e10,
+     * lo_r = -1e20 (the reference's A.setZero(), b = 1e10).  Fewer than three vertices (all points coincident or collinear): all
+     * P rows are written that way -- the reference keeps its PREVIOUS hull there; the update is stateless. */
+    OSOT_ROWS_CONVEX_HULL = 16
 } osot_rows_kind;
 
 typedef struct {
     int kind;  /* osot_rows_kind */
-    int rows;  /* for COLLISION: max_pairs */
-    double d_threshold, detection_threshold, bound_scaling;
+    int rows;  /* for COLLISION: max_pairs; for CONVEX_HULL: contact points */
+    double d_threshold, detection_threshold, bound_scaling;   /* bound_scaling of CONVEX_HULL: the safety margin (metres) */
     int first_col;   /* unit-row / friction-cone / surface-contact blocks: column of the block's first variable */
     double dT, p;    /* acceleration limits: time step and horizon factor (dt = dT*p) */
     double mu;       /* friction coefficient */
@@ -280,6 +292,10 @@ typedef struct {
  *   ROWS_ACC_VELOCITY_LIMITS : p0 = qdot [B][rows], p1 = qdot_max [B][rows]
  *   ROWS_UNIT_GENERIC : p0 = lo [B][rows], p1 = up [B][rows]
  *   ROWS_TASK_CARTESIAN / ROWS_TASK_COM : as TASK_CARTESIAN / TASK_COM (the 6 / 3 rows are written by the producer into C)
+ *   ROWS_COP / ROWS_NORMAL_TORQUE / ROWS_WRENCH_FRICTION_CONE : p0 = wRl [B][contacts][9], p1 = x / y limits [B][contacts][4]
+ *   ROWS_CONVEX_HULL : p0 = CoM Jacobian [B][3][n] (rows 0 and 1 are read: what osot_kin_batch.com_J writes with
+ *                    com_J_stride = 3 n), p1 = CoM [B][3], p2 = world positions of the contact points [B][rows][3]
+ *                    (osot_kin_batch.points)
  * Task Jacobians are NOT passed here: the producer writes them straight into their row range of
  * osot_qp_batch.A[k] (zero-copy stacking; the reference copies them twice through MatrixPiler,
  * src/tasks/Aggregated.cpp:113-132).
@@ -574,6 +590,7 @@ int osot_qp_solve_batch_admm_warm(int B, int n, int nc, const double* H, const d
 #define OSOT_KIN_MAX_JOINTS 64
 #define OSOT_KIN_MAX_FRAMES 8
 #define OSOT_KIN_MAX_PAIRS 32
+#define OSOT_KIN_MAX_POINTS 16
 enum { OSOT_JOINT_REVOLUTE = 0, OSOT_JOINT_PRISMATIC = 1 };
 typedef struct {
     int n;                                   /* joints = generalised coordinates; tree order: parent[j] < j     */
@@ -634,6 +651,12 @@ typedef struct {
      *           joints both chains share drop out exactly, the joints of the base's own chain enter with a minus sign.
      * With frame_body[f] the rotation is R_d' instead (Ad(bR_d') after the R_b' of the relative Jacobian, Cartesian.cpp:93-100). */
     int frame_base[OSOT_KIN_MAX_FRAMES];
+    /* CONTACT POINTS (velocity::ConvexHull: convex_hull::getSupportPolygonPoints asks the model for getPose(link).translation() of
+     * every link in contact, src/utils/convex_hull_utils.cpp:142-174): point i is fixed at point_p[i] in the frame of joint
+     * point_joint[i]'s link; the producer writes its world position to osot_kin_batch.points.  All zero = none. */
+    int n_points;                                /* 0 .. OSOT_KIN_MAX_POINTS                                          */
+    int point_joint[OSOT_KIN_MAX_POINTS];        /* 0 .. n - 1                                                        */
+    double point_p[OSOT_KIN_MAX_POINTS][3];
 } osot_kin_desc;
 enum { OSOT_SHAPE_CAPSULE = 0, OSOT_SHAPE_BOX = 1 };
 #define OSOT_KIN_MAX_ENV 16
@@ -653,6 +676,8 @@ typedef struct {
     const double* env_pose;                        /* [n_env][12] world_T_shape = [R row-major | p] of the environment
                                                       shapes (moveCollisionShape), or NULL when n_env = 0           */
     long long env_pose_stride;                     /* 0: one world shared by all instances; 12 n_env: per instance  */
+    double* points;                                /* [B][n_points][3] world positions of the contact points (the
+                                                      OSOT_ROWS_CONVEX_HULL leaf p2), or NULL                        */
 } osot_kin_batch;
 typedef struct osot_kin osot_kin;
 int osot_kin_create(const osot_kin_desc* desc, int device, osot_kin** out);

@@ -17,6 +17,9 @@ BOUND_GENERIC, BOUND_JOINT_LIMITS, BOUND_VELOCITY_LIMITS = range(3)
  ROWS_ACC_JOINT_LIMITS, ROWS_ACC_VELOCITY_LIMITS, ROWS_TASK_CARTESIAN, ROWS_TASK_COM, ROWS_UNIT_GENERIC) = range(10)
 # surface contacts: 6-D wrenches, 5 / 4 / 8 stored rows per contact (force::FrictionCone, force::CoP, force::NormalTorque)
 ROWS_WRENCH_FRICTION_CONE, ROWS_COP, ROWS_NORMAL_TORQUE = 10, 11, 12
+# velocity::ConvexHull: rows = contact points (3 .. 16), built on the device from the CoM, its Jacobian and the points.  13 .. 15 are
+# not kinds (the validators refuse them as unknown)
+ROWS_CONVEX_HULL = 16
 # OpenSoT::HessianType (include/OpenSoT/Task.h:33-41)
 HST_UNDEFINED, HST_ZERO, HST_IDENTITY, HST_POSDEF, HST_POSDEF_NULLSPACE, HST_SEMIDEF, HST_UNKNOWN = range(7)
 
@@ -113,6 +116,7 @@ class IdModel(C.Structure):
 # every symbol include/osot_mi355x.h declares (tests/test_abi_symbols.py checks the .so exports all)
 KIN_MAX_JOINTS, KIN_MAX_FRAMES, KIN_MAX_PAIRS = 64, 8, 32
 KIN_MAX_ENV = 16
+KIN_MAX_POINTS = 16
 SHAPE_CAPSULE, SHAPE_BOX = 0, 1
 JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
 
@@ -131,7 +135,8 @@ class KinDesc(C.Structure):
                 ("pair_kind", C.c_int * KIN_MAX_PAIRS), ("pair_env", C.c_int * KIN_MAX_PAIRS),
                 ("pair_box", (C.c_double * 3) * KIN_MAX_PAIRS), ("pair_shape_R", (C.c_double * 9) * KIN_MAX_PAIRS),
                 ("pair_shape_p", (C.c_double * 3) * KIN_MAX_PAIRS), ("n_env", C.c_int),
-                ("frame_base", C.c_int * KIN_MAX_FRAMES)]
+                ("frame_base", C.c_int * KIN_MAX_FRAMES),
+                ("n_points", C.c_int), ("point_joint", C.c_int * KIN_MAX_POINTS), ("point_p", (C.c_double * 3) * KIN_MAX_POINTS)]
 
 
 class KinBatch(C.Structure):
@@ -139,7 +144,7 @@ class KinBatch(C.Structure):
                 ("frame_J", C.c_void_p * KIN_MAX_FRAMES), ("frame_J_stride", C.c_longlong * KIN_MAX_FRAMES),
                 ("com", C.c_void_p), ("com_J", C.c_void_p), ("com_J_stride", C.c_longlong),
                 ("pair_dist", C.c_void_p), ("pair_J", C.c_void_p), ("pair_J_stride", C.c_longlong),
-                ("env_pose", C.c_void_p), ("env_pose_stride", C.c_longlong)]
+                ("env_pose", C.c_void_p), ("env_pose_stride", C.c_longlong), ("points", C.c_void_p)]
 
 
 class DynDesc(C.Structure):

@@ -229,6 +229,8 @@ inline int make_update_args(const osot_plan_desc& pl, const DevUpdatePlan& PL, c
         if (kind == OSOT_ROWS_GENERIC && !d.p2) { *why = "generic rows need C, lo, up"; return OSOT_ERR_INVALID; }
         if ((kind == OSOT_ROWS_COP || kind == OSOT_ROWS_NORMAL_TORQUE) && !d.p1)
             { *why = "CoP / normal torque rows need the contact's x / y limits (p1)"; return OSOT_ERR_INVALID; }
+        if (kind == OSOT_ROWS_CONVEX_HULL && (!d.p1 || !d.p2))
+            { *why = "convex hull rows need the CoM Jacobian (p0), the CoM (p1) and the contact points (p2)"; return OSOT_ERR_INVALID; }
     }
     if (PL.nc > 0 && (!out->lo || !out->up)) { *why = "out.lo/up is null"; return OSOT_ERR_INVALID; }
     if (PL.nc_stored > 0 && !out->C) { *why = "out.C is null"; return OSOT_ERR_INVALID; }

@@ -949,6 +949,93 @@ __device__ inline double wrench_row_entry(int kind, int rr, int col, const doubl
     return a[o] * R[c * 3 + 0] + a[o + 1] * R[c * 3 + 1] + a[o + 2] * R[c * 3 + 2];
 }
 
+// ---- velocity::ConvexHull (src/constraints/velocity/ConvexHull.cpp:41-134, src/utils/convex_hull_utils.cpp:142-174) ----
+// sign of cross(u, v) = u.x v.y - u.y v.x, taken as the COMPARISON of its two rounded products: the difference of two doubles is
+// zero only when they are equal and has the sign of their order, so this is the sign of the expression as written -- and no
+// multiply-add contraction can touch it.  Exactly antisymmetric: hull_turn(u, v) == -hull_turn(v, u).  No epsilon.
+__device__ inline int hull_turn(double ux, double uy, double vx, double vy) {
+    const double l = ux * vy, r = uy * vx;
+    return l > r ? 1 : (l < r ? -1 : 0);
+}
+// The rows of one OSOT_ROWS_CONVEX_HULL block of one instance by the wavefront (t = lane).  xy: 4 * OSOT_KIN_MAX_POINTS doubles of LDS.
+//   points   lane i < P: (x_i, y_i) = (p_i - com)[0:2] -> LDS (CoM-relative, projected on z = 0: convex_hull_utils.cpp:161-167,
+//            projectPCL2Plane)
+//   vertices lane i looks for its counter-clockwise successor: a point j != p_i with EVERY point on or left of i -> j.  Any two
+//            such j are collinear with i (each is on or left of the other's ray); the farthest in the first one's direction is
+//            taken.  i is a vertex iff it is no duplicate of a lower-indexed point, has a successor, and no point lies behind it
+//            on the successor's line (a point between two others is no vertex).  At most P^2 + 2 P sign tests per lane, no sort.
+//   rows     row r = the r-th vertex in order of POINT INDEX (ballot + prefix count), the edge to its successor:
+//            getLineCoefficients a = y_i - y_j, b = x_j - x_i, c = -b y_i - a x_i; getConstraints keeps (a, b) with bound -c when
+//            c <= 0 and takes (-a, -b) with bound c otherwise ("feasible at the start": a CoM outside the polygon flips the row),
+//            then bound -= margin sqrt(a^2 + b^2).  C_r = a J_x + b J_y, up_r = bound, lo_r = -1e20.
+//   the rest rows at or beyond the vertex count -- all P of them with fewer than 3 vertices (points coincident or collinear) --
+//            are C_r = 0, up_r = 1e10, lo_r = -1e20 (A.setZero(), b = 1e10).  The reference keeps its previous hull in the
+//            degenerate case; this update has no memory.
+// Written without contraction: the same bits in every kernel, and the bits of the expressions as written.
+// NOT inlined: as part of update_body it moved the register allocation of the fused kernels, which sit at their limits
+// (profiles/convex_hull_kernel_resources.txt); as a call it costs a plan with the block a few hundred clocks and the others nothing.
+__device__ inline __attribute__((noinline)) void convex_hull_rows(const DevRowBlockS& rb, const DevPtr3& rp, const long long inst, const int n, const int t,
+                                        double* Cb, double* lob, double* upb, double* xy) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const int P = rb.rows;
+    double* ab = xy + 2 * OSOT_KIN_MAX_POINTS;   // (a, b) of every row
+    const int i = t < P ? t : 0;
+    const double xi = rp.p2[(inst * P + i) * 3] - rp.p1[inst * 3];
+    const double yi = rp.p2[(inst * P + i) * 3 + 1] - rp.p1[inst * 3 + 1];
+    if (t < P) { xy[2 * t] = xi; xy[2 * t + 1] = yi; }
+    __syncthreads();
+    bool vertex = false;
+    int succ = 0;
+    if (t < P) {
+        bool dup = false;
+        for (int k = 0; k < t; ++k) dup = dup || (xy[2 * k] == xi && xy[2 * k + 1] == yi);
+        int s = -1;
+        double sx = 0.0, sy = 0.0;
+        for (int j = 0; j < P; ++j) {
+            const double ux = xy[2 * j] - xi, uy = xy[2 * j + 1] - yi;
+            if (ux == 0.0 && uy == 0.0) continue;
+            bool ok = true;
+            for (int k = 0; k < P; ++k) ok = ok && hull_turn(ux, uy, xy[2 * k] - xi, xy[2 * k + 1] - yi) >= 0;
+            if (!ok) continue;
+            const bool same = (sx != 0.0) ? ((ux > 0.0) == (sx > 0.0)) : ((uy > 0.0) == (sy > 0.0));
+            if (s < 0 || (same && (fabs(ux) > fabs(sx) || fabs(uy) > fabs(sy)))) { s = j; sx = ux; sy = uy; }
+        }
+        bool behind = false;
+        for (int k = 0; k < P && s >= 0; ++k) {
+            const double vx = xy[2 * k] - xi, vy = xy[2 * k + 1] - yi;
+            if ((vx == 0.0 && vy == 0.0) || hull_turn(sx, sy, vx, vy) != 0) continue;
+            const bool same = (sx != 0.0) ? ((vx > 0.0) == (sx > 0.0)) : ((vy > 0.0) == (sy > 0.0));
+            behind = behind || !same;
+        }
+        vertex = !dup && s >= 0 && !behind;
+        succ = s < 0 ? 0 : s;
+    }
+    const unsigned long long vmask = wave_ballot(vertex);
+    const int nv = __builtin_popcountll(vmask) >= 3 ? __builtin_popcountll(vmask) : 0;
+    const int r = lanes_below(vmask);
+    if (vertex && nv > 0) {
+        const double xj = xy[2 * succ], yj = xy[2 * succ + 1];
+        const double a = yi - yj, b = xj - xi;
+        const double c = -b * yi - a * xi;
+        const bool keep = c <= 0.0;
+        ab[2 * r] = keep ? a : -a;
+        ab[2 * r + 1] = keep ? b : -b;
+        upb[r] = (keep ? -c : c) - rb.bound_scaling * sqrt(a * a + b * b);
+        lob[r] = -1.0e20;
+    }
+    if (t < P && t >= nv) { upb[t] = 1.0e10; lob[t] = -1.0e20; }
+    __syncthreads();
+    const double* Jx = rp.p0 + inst * 3LL * n;
+    const double* Jy = Jx + n;
+    for (int col = t; col < n; col += 64) {
+        const double jx = Jx[col], jy = Jy[col];
+        for (int q = 0; q < P; ++q) Cb[q * n + col] = (q < nv) ? ab[2 * q] * jx + ab[2 * q + 1] * jy : 0.0;
+    }
+    __syncthreads();   // (the scratch belongs to the next block)
+}
+
 // AutoStack::update() of one instance by one wavefront.  `args_global` = the kernel's DevUpdate as MEMORY (the kernarg
 // segment), `lds` = kUpdateLdsBytes of LDS.  First the per-call pointers and the static plan are staged into LDS by ONE
 // batch of 16-byte vector loads (6 per lane): after that every lane looks up its row's task, gains and pointers with
@@ -1220,6 +1307,8 @@ __device__ __forceinline__ void update_body(const DevUpdate* args_global, const 
                 Cb[(ct * per + rr) * n + rb.first_col + ct * 6 + col] = wrench_row_entry(rb.kind, rr, col, R, lim, rb.mu);
             }
             for (int r = t; r < rb.rows; r += 64) { lob[r] = -1.0e20; upb[r] = 0.0; }
+        } else if (rb.kind == OSOT_ROWS_CONVEX_HULL) {   // velocity::ConvexHull: the collision block's scratch holds the points
+            convex_hull_rows(rb, rp, inst, n, t, Cb, lob, upb, dcand);
         } else if (rb.kind == 5) {   // acceleration::JointLimits (constraints/acceleration/JointLimits.cpp:58-176)
             const int nr = rb.rows;
             const double dt = rb.dT * rb.p;

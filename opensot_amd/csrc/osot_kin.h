@@ -10,6 +10,7 @@
 //      once: one coalesced 8 n-byte store per row, straight into the stacked A_k.
 //   4. centre of mass: c = sum m_l c_l / M (wave reduction); column j of its Jacobian from the subtree aggregates
 //      (mass and first moment of the links joint j moves): z_j x (Sc_j - Sm_j p_j) / M  (prismatic: (Sm_j / M) z_j)
+//   3b. contact points (lane = point): world position of a point fixed in a link -> the convex-hull rows' leaf
 //   5. self-collision pairs (capsule / sphere pairs): lane p = pair for the closest points of the two axis segments
 //      (world frame) -> distance d = |c_a - c_b| - r_a - r_b and unit normal n -> LDS; then one coalesced row per
 //      pair, lane j = joint: J_d[j] = n . (v_j(c_a) [j moves a] - v_j(c_b) [j moves b]),  v_j(c) = z_j x (c - p_j)
@@ -63,6 +64,14 @@ inline int kin_check_frames(const osot_kin_desc* d, const char** why) {
             *why = "frame_base must be 0 (world) or 1 + the index of another frame";
             return OSOT_ERR_INVALID;
         }
+    return OSOT_OK;
+}
+
+// ... and of the contact points (osot_kin_desc.point_*)
+inline int kin_check_points(const osot_kin_desc* d, const char** why) {
+    if (d->n_points < 0 || d->n_points > OSOT_KIN_MAX_POINTS) { *why = "contact point count out of range (0..16)"; return OSOT_ERR_INVALID; }
+    for (int i = 0; i < d->n_points; ++i)
+        if (d->point_joint[i] < 0 || d->point_joint[i] >= d->n) { *why = "contact point attached to a joint out of range"; return OSOT_ERR_INVALID; }
     return OSOT_OK;
 }
 
@@ -171,6 +180,20 @@ __device__ inline void closest_segment_box(const double* p0, const double* p1, c
 #ifndef OSOT_KIN_TS
 #define OSOT_KIN_TS 12
 #endif
+// contact points, lane = point: R_w p + p_w of the point's joint from the world transforms Tw in LDS -> points [B][n_points][3], the
+// OSOT_ROWS_CONVEX_HULL leaf p2 (convex_hull::getSupportPolygonPoints: getPose(link).translation()).  Not inlined: the producer's
+// kernels keep their register allocation (profiles/convex_hull_kernel_resources.txt).
+__device__ inline __attribute__((noinline)) void kin_points(const DevKin* __restrict__ K, double* points, const long long inst, const int j, const double* Tw) {
+    constexpr int TS = OSOT_KIN_TS;
+    const int np = K->d.n_points;
+    if (j >= np) return;
+    const int jp = K->d.point_joint[j];
+    const double lp[3] = {K->d.point_p[j][0], K->d.point_p[j][1], K->d.point_p[j][2]};
+    double wp[3];
+    mat3_vec(Tw + jp * TS, lp, wp);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) points[(inst * np + j) * 3 + i] = wp[i] + Tw[jp * TS + 9 + i];
+}
 // LDS one instance of kin_instance needs, in doubles (the int / 64-bit tables included): transforms, axes, centres of mass, parents,
 // ancestor masks -- and the pair table of the PAIRS instantiation
 template <int JMAX> constexpr int kin_lds_doubles(bool pairs) {
@@ -368,6 +391,8 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
             }
         }
     }
+    // ---- 3b. contact points (the world transforms in LDS are unchanged since the barrier of 3a)
+    if (Bt.points && K->d.n_points > 0 && live) kin_points(K, Bt.points, inst, j, Tw);
     KIN_PHASE("world");
     // ---- 3. frames: the Jacobian columns, lane = joint
     // (a frame's transform and options come from the LDS table in one batch of reads -- fetched from the model here, every frame started

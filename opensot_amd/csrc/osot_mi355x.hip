@@ -197,9 +197,10 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
     OSOT_LAYOUT_BEGIN(osot_kin_desc) OSOT_F(n) OSOT_F(parent) OSOT_F(type) OSOT_F(axis) OSOT_F(R0) OSOT_F(p0) OSOT_F(mass) OSOT_F(com)
         OSOT_F(n_frames) OSOT_F(frame_joint) OSOT_F(frame_R) OSOT_F(frame_p) OSOT_F(n_pairs) OSOT_F(pair_joint) OSOT_F(pair_seg)
         OSOT_F(pair_radius) OSOT_F(frame_body) OSOT_F(frame_col_mask) OSOT_F(com_col_mask) OSOT_F(pair_kind) OSOT_F(pair_env)
-        OSOT_F(pair_box) OSOT_F(pair_shape_R) OSOT_F(pair_shape_p) OSOT_F(n_env) OSOT_F(frame_base) OSOT_LAYOUT_END()
+        OSOT_F(pair_box) OSOT_F(pair_shape_R) OSOT_F(pair_shape_p) OSOT_F(n_env) OSOT_F(frame_base)
+        OSOT_F(n_points) OSOT_F(point_joint) OSOT_F(point_p) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_kin_batch) OSOT_F(B) OSOT_F(q) OSOT_F(frame_pose) OSOT_F(frame_J) OSOT_F(frame_J_stride) OSOT_F(com)
-        OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(pair_dist) OSOT_F(pair_J) OSOT_F(pair_J_stride) OSOT_F(env_pose) OSOT_F(env_pose_stride) OSOT_LAYOUT_END()
+        OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(pair_dist) OSOT_F(pair_J) OSOT_F(pair_J_stride) OSOT_F(env_pose) OSOT_F(env_pose_stride) OSOT_F(points) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_desc) OSOT_F(inertia) OSOT_F(gravity) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_batch) OSOT_F(B) OSOT_F(q) OSOT_F(qdot) OSOT_F(M) OSOT_F(M_stride) OSOT_F(h) OSOT_F(frame_Jdot_qdot)
         OSOT_F(frame_Jdot_qdot_stride) OSOT_F(com_Jdot_qdot) OSOT_F(com_Jdot_qdot_stride) OSOT_LAYOUT_END()
@@ -1110,6 +1111,11 @@ int osot_kin_create(const osot_kin_desc* d, int device, osot_kin** out) {
     }
     if (d->n_pairs < 0 || d->n_pairs > OSOT_KIN_MAX_PAIRS) return fail(OSOT_ERR_INVALID, "collision pair count out of range");
     if (d->n_env < 0 || d->n_env > OSOT_KIN_MAX_ENV) return fail(OSOT_ERR_INVALID, "environment shape count out of range");
+    {
+        const char* why = "";
+        const int rc = kin_check_points(d, &why);
+        if (rc != OSOT_OK) return fail(rc, why);
+    }
     for (int p = 0; p < d->n_pairs; ++p) {
         if (d->pair_joint[p][0] < 0 || d->pair_joint[p][0] >= d->n) return fail(OSOT_ERR_INVALID, "collision shape attached to a joint out of range");
         if (d->pair_joint[p][1] < -1 || d->pair_joint[p][1] >= d->n)      // (-1: side b is a world / environment shape)

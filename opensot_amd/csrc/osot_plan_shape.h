@@ -156,7 +156,9 @@ inline int plan_validate(const osot_plan_desc* p, const char** why, int wide = 0
         if (p->bound[j].kind < 0 || p->bound[j].kind > OSOT_BOUND_VELOCITY_LIMITS) { *why = "unknown bound kind"; return OSOT_ERR_UNSUPPORTED; }
     for (int j = 0; j < p->n_rowblocks; ++j) {
         const osot_rows_desc& rb = p->rowblock[j];
-        if (rb.kind < 0 || rb.kind > OSOT_ROWS_NORMAL_TORQUE) { *why = "unknown row-block kind"; return OSOT_ERR_UNSUPPORTED; }
+        if ((rb.kind < 0 || rb.kind > OSOT_ROWS_NORMAL_TORQUE) && rb.kind != OSOT_ROWS_CONVEX_HULL) { *why = "unknown row-block kind"; return OSOT_ERR_UNSUPPORTED; }
+        if (rb.kind == OSOT_ROWS_CONVEX_HULL && (rb.rows < 3 || rb.rows > OSOT_KIN_MAX_POINTS)) {
+            *why = "convex hull block: rows = contact points, 3..16"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_TASK_CARTESIAN && rb.rows != 6) { *why = "a Cartesian task as a constraint has 6 rows"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_TASK_COM && rb.rows != 3) { *why = "a CoM task as a constraint has 3 rows"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_TASK_CARTESIAN || rb.kind == OSOT_ROWS_TASK_COM)

@@ -44,6 +44,35 @@ class KinModel:
     # rotational inertia [n][6] (Ixx Ixy Ixz Iyy Iyz Izz) of the link every joint moves, about its centre of mass, axes of the joint
     # frame (osot_dyn_desc.inertia: the dynamics producer, opensot_amd/dynamics.py); None = point masses
     inertia: np.ndarray = None
+    # contact points (velocity::ConvexHull's links in contact): (joint index, p[3] in that joint's link frame); their world positions
+    # are the producer's `points` output, the OSOT_ROWS_CONVEX_HULL leaf p2
+    points: list = field(default_factory=list)
+
+    def add_point(self, link_or_joint, p=(0.0, 0.0, 0.0)):
+        """a contact point fixed at p in the frame of a joint's link (joint index or name) -> its index"""
+        j = self.names.index(link_or_joint) if isinstance(link_or_joint, str) else int(link_or_joint)
+        if not 0 <= j < self.n:
+            raise ValueError(f"contact point: joint {link_or_joint!r} is not in the model")
+        if len(self.points) >= abi.KIN_MAX_POINTS:
+            raise ValueError(f"the producer holds {abi.KIN_MAX_POINTS} contact points")
+        self.points.append((j, tuple(float(v) for v in p)))
+        return len(self.points) - 1
+
+    def points_world(self, q):
+        """numpy restatement of the producer's `points` output for one configuration q[n]: [n_points][3]"""
+        q = np.asarray(q, dtype=float)
+        Rw, pw = np.zeros((self.n, 3, 3)), np.zeros((self.n, 3))
+        for j in range(self.n):
+            if self.jtype[j] == abi.JOINT_REVOLUTE:
+                x, y, z = self.axis[j]
+                c, s = np.cos(q[j]), np.sin(q[j])
+                K = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+                Rl, pl = self.R0[j] @ (np.eye(3) + s * K + (1.0 - c) * (K @ K)), self.p0[j]      # Rodrigues
+            else:
+                Rl, pl = self.R0[j], self.p0[j] + self.R0[j] @ self.axis[j] * q[j]
+            a = self.parent[j]
+            Rw[j], pw[j] = (Rl, pl) if a < 0 else (Rw[a] @ Rl, Rw[a] @ pl + pw[a])
+        return np.array([Rw[j] @ np.asarray(p) + pw[j] for j, p in self.points]).reshape(len(self.points), 3)
 
     # ---- the reference's three calls ------------------------------------------------------------------------------
     def add_collision_shape(self, name, link, shape, link_T_shape=None):
@@ -160,6 +189,11 @@ class KinModel:
                 raise ValueError(f"frame {f}: its base link frame must be another frame of the model")
             d.frame_base[f] = g + 1
         d.com_col_mask = mask(self.com_active_joints) if self.com_active_joints is not None else 0
+        d.n_points = len(self.points)
+        for i, (j, p) in enumerate(self.points):
+            d.point_joint[i] = int(j)
+            for c in range(3):
+                d.point_p[i][c] = float(p[c])
         d.n_pairs = len(self.pairs)
         d.n_env = sum(1 for e in self.env_shapes if e["link"] == "world")
         for k, pr in enumerate(self.pairs):
@@ -300,17 +334,18 @@ class Kinematics:
         except Exception:
             pass
 
-    def forward(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None):
+    def forward(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None):
         """osot_kinematics for the batch `batch_args` describes, stream-ordered on torch's current stream"""
-        kb = self.batch_args(q, frame_pose, frame_J, com, com_J, pair_dist, pair_J, env_pose)
+        kb = self.batch_args(q, frame_pose, frame_J, com, com_J, pair_dist, pair_J, env_pose, points)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         abi.check(self._lib.osot_kinematics(self._h, C.byref(kb), stream), "osot_kinematics")
 
-    def batch_args(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None):
+    def batch_args(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None):
         """the osot_kin_batch of a call (pointers and strides only; the tensors must outlive its use).  q [B][n] (device).  frame_pose: {frame index: tensor [B][12]}; frame_J: {frame index: (A_k tensor [B][ma][n],
         first row)}; com: tensor [B][3]; com_J: (A_k tensor, first row).
         env_pose: poses of the environment shapes, a device tensor [n_env][12] (one world for all instances) or
-        [B][n_env][12]; default: the model's own (add_collision_shape / move_collision_shape), uploaded when they change"""
+        [B][n_env][12]; default: the model's own (add_collision_shape / move_collision_shape), uploaded when they change.
+        points: tensor [B][n_points][3], the world positions of the model's contact points (add_point)"""
         B, n = q.shape
         assert n == self.model.n and q.is_contiguous()
         kb = abi.KinBatch()
@@ -330,6 +365,10 @@ class Kinematics:
             assert A.is_contiguous() and A.shape[2] == n and row + 3 <= A.shape[1]
             kb.com_J = A.data_ptr() + 8 * row * n
             kb.com_J_stride = A.shape[1] * n
+        if points is not None:         # [B][n_points][3]: the OSOT_ROWS_CONVEX_HULL leaf p2
+            assert points.is_contiguous() and points.dtype == torch.float64 and points.shape[0] >= B
+            assert tuple(points.shape[1:]) == (len(self.model.points), 3)
+            kb.points = points.data_ptr()
         if pair_dist is not None:      # [B][n_pairs]: the OSOT_ROWS_COLLISION leaf p1
             assert pair_dist.is_contiguous() and pair_dist.shape[1] == len(self.model.pairs)
             kb.pair_dist = pair_dist.data_ptr()

@@ -85,7 +85,7 @@ class Rows:
     rows: int
     d_threshold: float = 0.0
     detection_threshold: float = 0.0
-    bound_scaling: float = 1.0
+    bound_scaling: float = 1.0   # ROWS_CONVEX_HULL: the safety margin in metres (ConvexHull::setSafetyMargin)
     name: str = ""
     first_col: int = 0
     dT: float = 0.0
@@ -174,6 +174,9 @@ class StackPlan:
                 if t.kind in (abi.TASK_COM, abi.TASK_ACC_COM):
                     assert t.rows == 3
         assert len(self.bounds) <= abi.MAX_BOUNDS and len(self.rowblocks) <= abi.MAX_ROWBLOCKS
+        for r in self.rowblocks:
+            if r.kind == abi.ROWS_CONVEX_HULL:   # rows = contact points = the fixed row count (stored rows: not in UNIT_ROW_BLOCKS)
+                assert 3 <= r.rows <= abi.KIN_MAX_POINTS, "convex hull block: 3 .. 16 contact points"
         if self.regularisation is not None:
             r = self.regularisation
             assert not r.row_mask

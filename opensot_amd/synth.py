@@ -711,3 +711,105 @@ def make_coman_id_stack(B, seed=None, tree=None, inertia=None, eps_factor=1e6):
     leaf = {"B": B, "A": [z(B, 15, n), None], "task": tleaf, "bound": [], "rows": rleaf, "C": [None] * 4,
             "state": {"q0": q0, "qdot0": z(B, nv), "q_ref": q_ref}, "contacts": ("l_sole", "r_sole"), "nv": nv}
     return plan, leaf, model
+
+
+# the sole rectangle around a sole frame's origin (x_l, x_u, y_l, y_u): the CoP limits of make_coman_id_stack, and the corners of the
+# support polygon of make_coman_balance_stack
+SOLE_RECTANGLE = (-0.06, 0.12, -0.045, 0.045)
+
+
+def make_balance_stack(B, seed=None, n=32, P=8, margin=0.002, eps_factor=1e6):
+    """A velocity stack with the balance constraint of the reference's walking / whole-body IK stacks,
+    `(com / postural) << joint_limits << velocity_limits << convex_hull` (constraints::velocity::ConvexHull, ConvexHull.cpp:41-134):
+
+    levels : 0 = velocity::CoM (3 rows; its Jacobian is the hull block's leaf p0: one [B][3][n] array), 1 = velocity::Postural
+    box    : joint limits, velocity limits
+    rows   : OSOT_ROWS_CONVEX_HULL on P contact points, safety margin `margin`
+
+    Model quantities are synthetic: com_J ~ N(0, 0.3^2), the contact points a polygon around the CoM (in shuffled order, a quarter of
+    them inside it), so dq = 0 is feasible; the CoM reference lies 0.1 .. 0.3 m away, beyond the polygon, so hull rows become active."""
+    rng = np.random.default_rng(11000 if seed is None else seed)
+    assert 3 <= P <= abi.KIN_MAX_POINTS
+    bounds, bleaf = _box_leaf(rng, B, n, jl=True, vl=True)
+    Jcom = rng.normal(0.0, 0.3, size=(B, 3, n))
+    com = rng.uniform(-0.2, 0.2, size=(B, 3))
+    ang = rng.uniform(0.0, 2.0 * np.pi, size=(B, 1))
+    pd = com + np.concatenate([np.cos(ang), np.sin(ang), np.zeros((B, 1))], axis=1) * rng.uniform(0.1, 0.3, size=(B, 1))
+    nh = max(3, P - P // 4)                                     # points on the polygon; the rest lie inside
+    th = 2.0 * np.pi * (np.arange(nh)[None, :] + rng.uniform(-0.15, 0.15, size=(B, nh))) / nh + rng.uniform(0.0, 2.0 * np.pi, size=(B, 1))
+    rad = rng.uniform(0.03, 0.06, size=(B, nh))
+    rad = np.concatenate([rad, rad[:, :P - nh] * rng.uniform(0.1, 0.4, size=(B, P - nh))], axis=1)
+    th = np.concatenate([th, rng.uniform(0.0, 2.0 * np.pi, size=(B, P - nh))], axis=1)
+    pts = np.stack([com[:, :1] + rad * np.cos(th), com[:, 1:2] + rad * np.sin(th), rng.uniform(-0.9, -0.8, size=(B, P))], axis=2)
+    pts = np.ascontiguousarray(np.take_along_axis(pts, np.argsort(rng.random((B, P)), axis=1)[:, :, None], axis=1))
+    q = bleaf[0][0]
+    levels = [[Task(abi.TASK_COM, 3, lam=1.0, name="com")], [Task(abi.TASK_POSTURAL, n, lam=0.01, name="postural")]]
+    tleaf = [[(com, pd, None)], [(q, q + rng.normal(0.0, 0.1, size=(B, n)), None)]]
+    rowblocks = [Rows(abi.ROWS_CONVEX_HULL, P, bound_scaling=margin, name="convex_hull")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [Jcom, None], "task": tleaf, "bound": bleaf, "rows": [(Jcom, com, pts)], "C": [None]}
+    return plan, leaf
+
+
+def make_coman_balance_stack(B, seed=None, tree=None, margin=0.02, eps_factor=1e6):
+    """The same stack on the reference's COMAN (35 coordinates) with every model quantity LEFT FOR THE KINEMATICS PRODUCER: the CoM, its
+    Jacobian (written into A_0, which is also the hull block's leaf p0) and the eight contact points -- the four corners of each sole
+    (SOLE_RECTANGLE around the l_sole / r_sole frames) on the two feet's links (KinModel.add_point).  A closed loop through
+    osot_control_cycle / osot_control_rollout never leaves the device: the polygon follows the posture.
+    The posture is a standing one, knees bent; the CoM reference lies `push` = 0.3 m ahead and to the side, beyond the polygon.
+    Returns (plan, leaf, model); leaf["state"] = q0, q_ref, push.  bind_balance() wires the device tensors."""
+    import os
+    from . import kinematics as kin
+    here = os.path.dirname(os.path.abspath(__file__))
+    model, lo, up = kin.from_json(tree or os.path.join(os.path.dirname(here), "tests", "golden", "coman_tree.json"))
+    rng = np.random.default_rng(12000 if seed is None else seed)
+    n = model.n
+    ix = model.names.index
+    xl, xu, yl, yu = SOLE_RECTANGLE
+    for name in ("l_sole", "r_sole"):
+        _, jf, Rf, pf = model.frames[model.frame_index(name)]
+        for cx, cy in ((xl, yl), (xu, yl), (xu, yu), (xl, yu)):
+            model.add_point(jf, np.asarray(pf, dtype=float) + np.asarray(Rf, dtype=float) @ np.array([cx, cy, 0.0]))
+    q0 = np.zeros((B, n))
+    for s_ in "LR":
+        q0[:, ix(s_ + "HipSag")] = -0.3; q0[:, ix(s_ + "KneeSag")] = 0.6; q0[:, ix(s_ + "AnkSag")] = -0.3
+        q0[:, ix(s_ + "Elbj")] = -0.8; q0[:, ix(s_ + "ShSag")] = 0.2
+    q0[:, ix("LShLat")] = 0.3; q0[:, ix("RShLat")] = -0.3
+    q0[:, 6:] += rng.normal(0.0, 0.02, (B, n - 6))
+    qmin, qmax = np.maximum(lo, -10.0), np.minimum(up, 10.0)
+    q0 = np.clip(q0, qmin + 1e-3, qmax - 1e-3)
+    q_ref = q0 + rng.uniform(-0.05, 0.05, (B, n))
+    ang = rng.uniform(0.0, 2.0 * np.pi, size=(B, 1))
+    push = 0.3 * np.concatenate([np.cos(ang), np.sin(ang), np.zeros((B, 1))], axis=1)
+    z = lambda *sh: np.zeros(sh)
+    levels = [[Task(abi.TASK_COM, 3, lam=1.0, name="com")], [Task(abi.TASK_POSTURAL, n, lam=0.1, name="postural")]]
+    bounds = [Bound(abi.BOUND_JOINT_LIMITS, scaling=1.0, name="joint_limits"), Bound(abi.BOUND_VELOCITY_LIMITS, dT=0.05, name="velocity_limits")]
+    rowblocks = [Rows(abi.ROWS_CONVEX_HULL, len(model.points), bound_scaling=margin, name="convex_hull")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, 3, n), None], "task": [[(z(B, 3), z(B, 3), None)], [(q0.copy(), q_ref, None)]],
+            "bound": [(q0.copy(), np.tile(qmin, (B, 1)), np.tile(qmax, (B, 1))), (np.full((B, n), 2.0), None, None)],
+            "rows": [(z(B, 3, n), z(B, 3), z(B, len(model.points), 3))], "C": [None],
+            "state": {"q0": q0, "q_ref": q_ref, "push": push}}
+    return plan, leaf, model
+
+
+def bind_balance(stack, kin, leaf):
+    """wire make_coman_balance_stack to the device: one q tensor is the producer's input, the Postural task's and the joint limits' q
+    (and what q_integrate advances); the producer writes the CoM into the CoM task's and the hull block's leaf, its Jacobian into
+    stack.A[0] (= the hull block's p0) and the contact points into the hull block's p2.  The CoM reference is the first posture's CoM
+    plus leaf["state"]["push"].  -> (dev_leaf, kin_batch, q)"""
+    import torch
+    B = leaf["B"]
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q = torch.as_tensor(leaf["state"]["q0"], **f64).contiguous()
+    com = torch.zeros((B, 3), **f64)
+    pts = torch.zeros((B, len(kin.model.points), 3), **f64)
+    kw = dict(com=com, com_J=(stack.A[0], 0), points=pts)
+    kin.forward(q, **kw)
+    com_ref = com.clone() + torch.as_tensor(leaf["state"]["push"], **f64)
+    dev["task"][0][0] = (com, com_ref, None)
+    dev["task"][1][0] = (q, dev["task"][1][0][1], None)
+    dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
+    dev["rows"][0] = (stack.A[0], com, pts)
+    return dev, kin.batch_args(q, **kw), q
