@@ -130,13 +130,20 @@ typedef struct {
 typedef enum {
     OSOT_BOUND_GENERIC = 0,        /* l,u supplied */
     OSOT_BOUND_JOINT_LIMITS = 1,   /* velocity::JointLimits (src/constraints/velocity/JointLimits.cpp:37-58) */
-    OSOT_BOUND_VELOCITY_LIMITS = 2 /* velocity::VelocityLimits (…/VelocityLimits.cpp:72-89) */
+    OSOT_BOUND_VELOCITY_LIMITS = 2,/* velocity::VelocityLimits (…/VelocityLimits.cpp:72-89) */
+    /* velocity::JointLimitsInvariance (src/constraints/velocity/JointLimitsInvariance.cpp:47-206): the velocity-IK box that also
+     * respects an acceleration limit.  dT = the control period dt (> 0), scaling = the step-ahead predictor p (0 < p <= 1,
+     * setPStepAheadPredictor).  Per joint, with s = q_max - q, i = q_min - q (q = the leaf's q - q_neutral) and v = qdot_prev:
+     *   ub = (v <= 0) ? min(s, dt^2 a + dt v) : min(via, dt^2 a + dt v), via = +-sqrt(|2 a dt^2 p s|) with the sign of s;
+     *   lb the mirror image (v >= 0; -a; i); lb > ub swaps the two.  qdot_prev is the leaf p2: the caller advances it
+     * (qdot_prev = dq / dt) between cycles, which is why osot_control_rollout refuses such a plan for steps > 1. */
+    OSOT_BOUND_JOINT_LIMITS_INVARIANCE = 3
 } osot_bound_kind;
 
 typedef struct {
     int kind;       /* osot_bound_kind */
-    double scaling; /* JointLimits boundScaling */
-    double dT;      /* VelocityLimits dT */
+    double scaling; /* JointLimits boundScaling; JOINT_LIMITS_INVARIANCE: the step-ahead predictor p */
+    double dT;      /* VelocityLimits dT; JOINT_LIMITS_INVARIANCE: dt */
 } osot_bound_desc;
 
 typedef enum {
@@ -188,15 +195,36 @@ typedef enum {
      * getConstraints picks it: c <= 0 keeps (a, b)), lo_r = -1e20.  Rows at or beyond the vertex count: C_r = 0, up_r = 1e10,
      * lo_r = -1e20 (the reference's A.setZero(), b = 1e10).  Fewer than three vertices (all points coincident or collinear): all
      * P rows are written that way -- the reference keeps its PREVIOUS hull there; the update is stateless. */
-    OSOT_ROWS_CONVEX_HULL = 16
+    OSOT_ROWS_CONVEX_HULL = 16,
+    /* (17 is not a kind either) */
+    /* The recursively feasible acceleration joint limits: unit rows e_(first_col+i) (NOT stored), like OSOT_ROWS_ACC_JOINT_LIMITS in
+     * every generic respect (first_col, only_level).  q below is the leaf's ONE q - q_neutral (the convention of
+     * OSOT_ROWS_ACC_JOINT_LIMITS): the reference takes the raw q in Viability's M2 / m2 and difference(q, neutral) elsewhere, which
+     * differ only for a model whose neutral posture is not zero.  min / max are std::min / std::max, `(b < a) ? b : a` and
+     * `(a < b) ? b : a`: a NaN second argument is ignored (a joint exactly on a limit at rest gives M2 = -0/0), unlike fmin / fmax. */
+    OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY = 18, /* acceleration::JointLimitsViability (src/constraints/acceleration/
+                                      JointLimitsViability.cpp:79-190): dt = dT*p (p >= 1 the step-ahead predictor, dT*p > 0);
+                                      ub = min(pos, (qdot_max - qdot)/dt, viability, qddot_max), lb the mirror image, ub < lb swaps the
+                                      two, then both are clamped into [-qddot_max, qddot_max] */
+    OSOT_ROWS_ACC_JOINT_LIMITS_ECBF = 19,      /* acceleration::JointLimitsECBF (…/JointLimitsECBF.cpp:36-71): ub = min(-(a1 + a2) qdot
+                                      + a1 a2 (q_max - q), a3 (qdot_max - qdot), qddot_max), lb the mirror image; swap and clamp as
+                                      above; a1, a2, a3 per joint (setAlpha1/2/3); dT and p are not read */
+    /* velocity::CartesianPositionConstraint (src/constraints/velocity/CartesianPositionConstraint.cpp:81-108): R half-spaces
+     * A_c x <= b_c on the position x of a link (POSITION_CARTESIAN) or of the CoM (POSITION_COM).  rows = R (1 .. 16), STORED rows
+     * written by every update: C = A_c J[0:3], up = (b_c - A_c x) * bound_scaling, lo = -1e20. */
+    OSOT_ROWS_POSITION_CARTESIAN = 20,
+    OSOT_ROWS_POSITION_COM = 21
+    /* a kind added behind 21 needs its own branch in update_body (opensot_amd/csrc/osot_kernels.h): the update kernel hands every
+     * kind from 18 upwards to limit_kind_rows, whose last branch is the position rows; the validators refuse 22 and above today */
 } osot_rows_kind;
 
 typedef struct {
     int kind;  /* osot_rows_kind */
-    int rows;  /* for COLLISION: max_pairs; for CONVEX_HULL: contact points */
-    double d_threshold, detection_threshold, bound_scaling;   /* bound_scaling of CONVEX_HULL: the safety margin (metres) */
+    int rows;  /* for COLLISION: max_pairs; for CONVEX_HULL: contact points; for POSITION_*: half-spaces */
+    double d_threshold, detection_threshold, bound_scaling;   /* bound_scaling of CONVEX_HULL: the safety margin (metres); of
+                                                                 POSITION_*: CartesianPositionConstraint's boundScaling */
     int first_col;   /* unit-row / friction-cone / surface-contact blocks: column of the block's first variable */
-    double dT, p;    /* acceleration limits: time step and horizon factor (dt = dT*p) */
+    double dT, p;    /* acceleration limits: time step and horizon factor (dt = dT*p); VIABILITY: p >= 1; ECBF: not read */
     double mu;       /* friction coefficient */
     double task_lambda, task_orientation_gain;   /* OSOT_ROWS_TASK_*: gains of the underlying task */
     double err_lb[OSOT_MAX_BAND_ROWS], err_ub[OSOT_MAX_BAND_ROWS];   /* OSOT_ROWS_TASK_*: TaskToConstraint's error band,
@@ -280,6 +308,7 @@ typedef struct {
  *   BOUND_JOINT_LIMITS    : p0 = q - q_neutral [B][n], p1 = q_min [B][n], p2 = q_max [B][n]
  *   BOUND_VELOCITY_LIMITS : p0 = qdot_max [B][n]
  *   BOUND_GENERIC         : p0 = l [B][n], p1 = u [B][n]
+ *   BOUND_JOINT_LIMITS_INVARIANCE : p0 = q - q_neutral [B][n], p1 = [q_min ; q_max ; qddot_max] [B][3*n], p2 = qdot_prev [B][n]
  *   ROWS_COLLISION : p0 = distance Jacobians J_d [B][rows][n] (ordered by distance), p1 = distances [B][rows]
  *   ROWS_GENERIC   : p0 = C [B][rows][n], p1 = lo [B][rows], p2 = up [B][rows]
  *   TASK_ACC_CARTESIAN / TASK_ACC_COM : p0 = [pose_err ; vel_err] [B][2*rows], p1 = Jdot*qdot [B][rows],
@@ -296,6 +325,13 @@ typedef struct {
  *   ROWS_CONVEX_HULL : p0 = CoM Jacobian [B][3][n] (rows 0 and 1 are read: what osot_kin_batch.com_J writes with
  *                    com_J_stride = 3 n), p1 = CoM [B][3], p2 = world positions of the contact points [B][rows][3]
  *                    (osot_kin_batch.points)
+ *   ROWS_ACC_JOINT_LIMITS_VIABILITY : p0 = [q - q_neutral ; qdot] [B][2*rows], p1 = [q_min ; q_max] [B][2*rows],
+ *                    p2 = [qdot_max ; qddot_max] [B][2*rows]
+ *   ROWS_ACC_JOINT_LIMITS_ECBF : p0, p1 as above, p2 = [qdot_max ; qddot_max ; a1 ; a2 ; a3] [B][5*rows]
+ *   ROWS_POSITION_CARTESIAN : p0 = the link's Jacobian [B][6][n] (rows 0 .. 2 are read: what osot_kin_batch.frame_J writes with
+ *                    frame_J_stride = 6 n), p1 = the link's pose [B][12] ([R row-major | p]; p is read), p2 = [A_c (rows x 3
+ *                    row-major) ; b_c (rows)] [B][4*rows]
+ *   ROWS_POSITION_COM : p0 = CoM Jacobian [B][3][n], p1 = CoM [B][3], p2 as for ROWS_POSITION_CARTESIAN
  * Task Jacobians are NOT passed here: the producer writes them straight into their row range of
  * osot_qp_batch.A[k] (zero-copy stacking; the reference copies them twice through MatrixPiler,
  * src/tasks/Aggregated.cpp:113-132).
@@ -703,7 +739,9 @@ int osot_control_cycle(osot_solver* s, osot_kin* k, const osot_kin_batch* kin_ba
  * planners ask for: B candidate roll-outs advanced K control cycles each.
  * q_integrate (required for steps > 1) is advanced by every cycle's dq; dq / status of the batch hold the LAST cycle's dq and the
  * FIRST non-zero status of the rollout (a failed cycle leaves the robot where it is: dq = 0, coman_ik.cpp:189-190);
- * dq_steps [steps][B][n] and status_steps [steps][B] (either may be NULL) receive every cycle's.  Stream-ordered. */
+ * dq_steps [steps][B][n] and status_steps [steps][B] (either may be NULL) receive every cycle's.  Stream-ordered.
+ * A plan with an OSOT_BOUND_JOINT_LIMITS_INVARIANCE bound is refused for steps > 1 (OSOT_ERR_UNSUPPORTED): its qdot_prev leaf is
+ * a held-fixed leaf input like any other, and the bound is only right when it follows every cycle's dq. */
 int osot_control_rollout(osot_solver* s, osot_kin* k, const osot_kin_batch* kin_batch, const osot_leaf_batch* leaf,
                          const osot_assembled_out* out, const osot_qp_batch* batch, double* q_integrate, int steps,
                          double* dq_steps, int* status_steps, void* hip_stream);

@@ -13,6 +13,8 @@ OK, ERR_INVALID, ERR_UNSUPPORTED, ERR_HIP, ERR_NOT_SOLVED, ERR_COMM = range(6)
 STATUS_SOLVED, STATUS_INFEASIBLE, STATUS_MAX_ITER, STATUS_NOT_PD = range(4)
 TASK_GENERIC, TASK_CARTESIAN, TASK_COM, TASK_POSTURAL, TASK_ACC_CARTESIAN, TASK_ACC_COM, TASK_ACC_POSTURAL = range(7)
 BOUND_GENERIC, BOUND_JOINT_LIMITS, BOUND_VELOCITY_LIMITS = range(3)
+# velocity::JointLimitsInvariance: dT = dt, scaling = the step-ahead predictor p (0 < p <= 1); leaf p2 = the previous cycle's velocity
+BOUND_JOINT_LIMITS_INVARIANCE = 3
 (ROWS_GENERIC, ROWS_COLLISION, ROWS_DYN_FEASIBILITY, ROWS_TORQUE_LIMITS, ROWS_FRICTION_CONE,
  ROWS_ACC_JOINT_LIMITS, ROWS_ACC_VELOCITY_LIMITS, ROWS_TASK_CARTESIAN, ROWS_TASK_COM, ROWS_UNIT_GENERIC) = range(10)
 # surface contacts: 6-D wrenches, 5 / 4 / 8 stored rows per contact (force::FrictionCone, force::CoP, force::NormalTorque)
@@ -20,6 +22,11 @@ ROWS_WRENCH_FRICTION_CONE, ROWS_COP, ROWS_NORMAL_TORQUE = 10, 11, 12
 # velocity::ConvexHull: rows = contact points (3 .. 16), built on the device from the CoM, its Jacobian and the points.  13 .. 15 are
 # not kinds (the validators refuse them as unknown)
 ROWS_CONVEX_HULL = 16
+# acceleration::JointLimitsViability / JointLimitsECBF: unit rows (not stored), like ROWS_ACC_JOINT_LIMITS; 17 is not a kind
+ROWS_ACC_JOINT_LIMITS_VIABILITY, ROWS_ACC_JOINT_LIMITS_ECBF = 18, 19
+# velocity::CartesianPositionConstraint on a link / on the CoM: rows = half-spaces (1 .. 16), stored rows built on the device
+ROWS_POSITION_CARTESIAN, ROWS_POSITION_COM = 20, 21
+MAX_POSITION_ROWS = 16
 # OpenSoT::HessianType (include/OpenSoT/Task.h:33-41)
 HST_UNDEFINED, HST_ZERO, HST_IDENTITY, HST_POSDEF, HST_POSDEF_NULLSPACE, HST_SEMIDEF, HST_UNKNOWN = range(7)
 

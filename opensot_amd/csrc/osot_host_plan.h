@@ -213,6 +213,8 @@ inline int make_update_args(const osot_plan_desc& pl, const DevUpdatePlan& PL, c
         if (!d.p0) { *why = "leaf input p0 of a bound is null"; return OSOT_ERR_INVALID; }
         if (kind == OSOT_BOUND_JOINT_LIMITS && (!d.p1 || !d.p2)) { *why = "joint limits need q, q_min, q_max"; return OSOT_ERR_INVALID; }
         if (kind == OSOT_BOUND_GENERIC && !d.p1) { *why = "generic bound needs l and u"; return OSOT_ERR_INVALID; }
+        if (kind == OSOT_BOUND_JOINT_LIMITS_INVARIANCE && (!d.p1 || !d.p2))
+            { *why = "joint limits invariance needs q (p0), [q_min; q_max; qddot_max] (p1) and qdot_prev (p2)"; return OSOT_ERR_INVALID; }
     }
     if (pl.n_bounds > 0 && (!out->l || !out->u)) { *why = "out.l/out.u is null"; return OSOT_ERR_INVALID; }
     U.l = out->l; U.u = out->u;
@@ -231,6 +233,10 @@ inline int make_update_args(const osot_plan_desc& pl, const DevUpdatePlan& PL, c
             { *why = "CoP / normal torque rows need the contact's x / y limits (p1)"; return OSOT_ERR_INVALID; }
         if (kind == OSOT_ROWS_CONVEX_HULL && (!d.p1 || !d.p2))
             { *why = "convex hull rows need the CoM Jacobian (p0), the CoM (p1) and the contact points (p2)"; return OSOT_ERR_INVALID; }
+        if ((kind == OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY || kind == OSOT_ROWS_ACC_JOINT_LIMITS_ECBF) && (!d.p1 || !d.p2))
+            { *why = "viability / ECBF joint limits need [q; qdot] (p0), [q_min; q_max] (p1) and the velocity / acceleration limits (p2)"; return OSOT_ERR_INVALID; }
+        if ((kind == OSOT_ROWS_POSITION_CARTESIAN || kind == OSOT_ROWS_POSITION_COM) && (!d.p1 || !d.p2))
+            { *why = "Cartesian position rows need the Jacobian (p0), the pose / CoM (p1) and [A_c; b_c] (p2)"; return OSOT_ERR_INVALID; }
     }
     if (PL.nc > 0 && (!out->lo || !out->up)) { *why = "out.lo/up is null"; return OSOT_ERR_INVALID; }
     if (PL.nc_stored > 0 && !out->C) { *why = "out.C is null"; return OSOT_ERR_INVALID; }

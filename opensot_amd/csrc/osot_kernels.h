@@ -1036,6 +1036,142 @@ __device__ inline __attribute__((noinline)) void convex_hull_rows(const DevRowBl
     __syncthreads();   // (the scratch belongs to the next block)
 }
 
+// ---- the recursively feasible joint limits and the Cartesian position constraint ----
+// std::min / std::max as the reference's compiler spells them: a NaN SECOND argument is ignored, a NaN first argument is returned.
+// JointLimitsViability relies on it: a joint exactly on a limit at rest has M2 = -0/0, and std::min(M1, NaN) is M1 -- fmin / fmax
+// agree there, but not when the NaN comes first, and the compiler may not reorder these.
+__device__ inline double std_min(double a, double b) { return (b < a) ? b : a; }
+__device__ inline double std_max(double a, double b) { return (a < b) ? b : a; }
+// The bounds of one OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY / _ECBF block of one instance, one lane per joint (t = lane):
+// acceleration::JointLimitsViability (src/constraints/acceleration/JointLimitsViability.cpp:79-190: accBoundsFromPosLimits,
+// accBoundsFromViability, computeJointAccBounds) and acceleration::JointLimitsECBF (JointLimitsECBF.cpp:36-71), every expression in
+// the reference's order of operations: min / max over the candidates, swap when ub < lb, then the clamp into +-qddot_max.
+// q is the leaf's q - q_neutral everywhere (the reference's M2 / m2 take the raw q: the same for a zero neutral posture).
+// Written without contraction: the same bits in every kernel, and the bits of the expressions as written.
+// Inlined into limit_kind_rows below, which is the call update_body makes.
+__device__ __forceinline__ void acc_bounds_store(double lb, double ub, const double amax, double* lo, double* up) {
+    if (ub < lb) { const double x = ub; ub = lb; lb = x; }
+    if (lb < -amax) lb = -amax;
+    if (ub > amax) ub = amax;
+    *lo = lb; *up = ub;
+}
+__device__ __forceinline__ void viability_bounds(const DevRowBlockS& rb, const DevPtr3& rp, const long long inst, const int t,
+                                                                  double* lob, double* upb) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const int nr = rb.rows;
+    const double dt = rb.p * rb.dT;
+    const double a = dt * dt;
+    for (int i = t; i < nr; i += 64) {
+        const double q = rp.p0[inst * 2 * nr + i], qd = rp.p0[inst * 2 * nr + nr + i];
+        const double qmin = rp.p1[inst * 2 * nr + i], qmax = rp.p1[inst * 2 * nr + nr + i];
+        const double vmax = rp.p2[inst * 2 * nr + i], amax = rp.p2[inst * 2 * nr + nr + i];
+        // accBoundsFromPosLimits
+        const double M1 = -qd / dt;
+        const double M2 = -(qd * qd) / (2.0 * (qmax - q));
+        const double M3 = 2.0 * (qmax - q - dt * qd) / a;
+        const double m2 = (qd * qd) / (2.0 * (q - qmin));
+        const double m3 = 2.0 * (qmin - q - dt * qd) / a;
+        double ub_pos, lb_pos;
+        if (qd >= 0.0) { lb_pos = m3; ub_pos = (M3 > M1) ? M3 : std_min(M1, M2); }
+        else { ub_pos = M3; lb_pos = (m3 < M1) ? m3 : std_max(M1, m2); }
+        // accBoundsFromViability
+        const double b1 = dt * (2.0 * qd + amax * dt);
+        const double c1 = qd * qd - 2.0 * amax * (qmax - q - dt * qd);
+        const double delta1 = b1 * b1 - 4.0 * a * c1;
+        const double ub_via = (delta1 >= 0.0) ? std_max(M1, (-b1 + sqrt(delta1)) / (2.0 * a)) : M1;
+        const double b2 = dt * (2.0 * qd - amax * dt);
+        const double c2 = qd * qd - 2.0 * amax * (q + dt * qd - qmin);
+        const double delta2 = b2 * b2 - 4.0 * a * c2;
+        const double lb_via = (delta2 >= 0.0) ? std_min(M1, (-b2 - sqrt(delta2)) / (2.0 * a)) : M1;
+        // computeJointAccBounds
+        const double ub_vel = (vmax - qd) / dt, lb_vel = (-vmax - qd) / dt;
+        acc_bounds_store(std_max(std_max(std_max(lb_pos, lb_vel), lb_via), -amax), std_min(std_min(std_min(ub_pos, ub_vel), ub_via), amax),
+                         amax, lob + i, upb + i);
+    }
+}
+__device__ __forceinline__ void ecbf_bounds(const DevRowBlockS& rb, const DevPtr3& rp, const long long inst, const int t,
+                                                             double* lob, double* upb) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const int nr = rb.rows;
+    for (int i = t; i < nr; i += 64) {
+        const double q = rp.p0[inst * 2 * nr + i], qd = rp.p0[inst * 2 * nr + nr + i];
+        const double qmin = rp.p1[inst * 2 * nr + i], qmax = rp.p1[inst * 2 * nr + nr + i];
+        const double* lim = rp.p2 + inst * 5LL * nr + i;
+        const double vmax = lim[0], amax = lim[nr], a1 = lim[2 * nr], a2 = lim[3 * nr], a3 = lim[4 * nr];
+        const double lower = -(a1 + a2) * qd + (a1 * a2) * (qmin - q);
+        const double upper = -(a1 + a2) * qd + (a1 * a2) * (qmax - q);
+        acc_bounds_store(std_max(std_max(lower, a3 * (-vmax - qd)), -amax), std_min(std_min(upper, a3 * (vmax - qd)), amax), amax, lob + i, upb + i);
+    }
+}
+// The rows of one OSOT_ROWS_POSITION_CARTESIAN / _COM block of one instance (velocity::CartesianPositionConstraint,
+// src/constraints/velocity/CartesianPositionConstraint.cpp:81-108): C = A_c J[0:3], one lane per column for each of the R rows;
+// up = (b_c - A_c x) * boundScaling, lo = -1e20, one lane per row.  J and x: the link's [6][n] Jacobian and the translation of its
+// pose, or the CoM's [3][n] Jacobian and the CoM.  Without contraction, and part of limit_kind_rows, as above.
+__device__ __forceinline__ void position_rows(const DevRowBlockS& rb, const DevPtr3& rp, const long long inst, const int n, const int t,
+                                                               double* Cb, double* lob, double* upb) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const int R = rb.rows;
+    const bool cart = rb.kind == OSOT_ROWS_POSITION_CARTESIAN;
+    const double* J = rp.p0 + inst * (cart ? 6LL : 3LL) * n;
+    const double* x = cart ? rp.p1 + inst * 12 + 9 : rp.p1 + inst * 3;
+    const double* Ac = rp.p2 + inst * 4LL * R;
+    const double* bc = Ac + 3 * R;
+    for (int col = t; col < n; col += 64) {
+        const double j0 = J[col], j1 = J[n + col], j2 = J[2 * n + col];
+        for (int r = 0; r < R; ++r) Cb[r * n + col] = Ac[3 * r] * j0 + Ac[3 * r + 1] * j1 + Ac[3 * r + 2] * j2;
+    }
+    for (int r = t; r < R; r += 64) {
+        upb[r] = (bc[r] - (Ac[3 * r] * x[0] + Ac[3 * r + 1] * x[1] + Ac[3 * r + 2] * x[2])) * rb.bound_scaling;
+        lob[r] = -1.0e20;
+    }
+}
+// The row kinds 18 .. 21 behind ONE call in update_body.  NOT inlined, like convex_hull_rows: update_body is part of the fused kernels,
+// whose register allocation sits at its limits; a plan without these blocks pays an untaken branch.  One function for the three
+// families, their bodies inlined into it: with a noinline function and a call site per family osot_update_kernel went from 120 to 122
+// VGPRs, with calls nested inside this one to 126 and 16 bytes of scratch (profiles/limit_kinds_kernel_resources.txt).
+__device__ inline __attribute__((noinline)) void limit_kind_rows(const DevRowBlockS& rb, const DevPtr3& rp, const long long inst, const int n, const int t,
+                                                                 double* Cb, double* lob, double* upb) {
+    if (rb.kind == OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY) viability_bounds(rb, rp, inst, t, lob, upb);
+    else if (rb.kind == OSOT_ROWS_ACC_JOINT_LIMITS_ECBF) ecbf_bounds(rb, rp, inst, t, lob, upb);
+    else position_rows(rb, rp, inst, n, t, Cb, lob, upb);   // 20, 21: plan_validate admits nothing above OSOT_ROWS_POSITION_COM
+}
+// One joint's box of OSOT_BOUND_JOINT_LIMITS_INVARIANCE (velocity::JointLimitsInvariance,
+// src/constraints/velocity/JointLimitsInvariance.cpp:47-206), the reference's branches and its sqrt(fabs(d)) sign logic as they are;
+// lb > ub swaps the two.  Returned by value (registers).  Not inlined and without contraction, as above.
+struct Box1 { double l, u; };
+__device__ inline __attribute__((noinline)) Box1 invariance_bound(const DevBoundS& bd, const DevPtr3& bp, const long long inst, const int n, const int i) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double dt = bd.dT, p = bd.scaling;
+    const double q = bp.p0[inst * n + i], v = bp.p2[inst * n + i];
+    const double qmin = bp.p1[inst * 3 * n + i], qmax = bp.p1[inst * 3 * n + n + i], amax = bp.p1[inst * 3 * n + 2 * n + i];
+    const double sup = qmax - q, inf = qmin - q;
+    double acc = dt * dt * amax + dt * v, ub, lb;
+    if (v <= 0.0) ub = (sup < acc) ? sup : acc;
+    else {
+        const double d = 2. * amax * dt * dt * p * sup;
+        const double via = (d < 0.) ? -sqrt(fabs(d)) : sqrt(d);
+        ub = (via < acc) ? via : acc;
+    }
+    acc = -dt * dt * amax + dt * v;
+    if (v >= 0.0) lb = (inf > acc) ? inf : acc;
+    else {
+        const double d = 2. * -amax * dt * dt * p * inf;
+        const double via = (d < 0.) ? sqrt(fabs(d)) : -sqrt(d);
+        lb = (via > acc) ? via : acc;
+    }
+    Box1 bx;
+    if (lb > ub) { bx.l = ub; bx.u = lb; } else { bx.l = lb; bx.u = ub; }
+    return bx;
+}
+
 // AutoStack::update() of one instance by one wavefront.  `args_global` = the kernel's DevUpdate as MEMORY (the kernarg
 // segment), `lds` = kUpdateLdsBytes of LDS.  First the per-call pointers and the static plan are staged into LDS by ONE
 // batch of 16-byte vector loads (6 per lane): after that every lane looks up its row's task, gains and pointers with
@@ -1198,6 +1334,9 @@ __device__ __forceinline__ void update_body(const DevUpdate* args_global, const 
                 } else if (bd.kind == 2) { // VelocityLimits.cpp:81-89
                     const double v = fabs(bp.p0[inst * n + i]) * bd.dT;
                     l2 = -1.0 * v; u2 = 1.0 * v;
+                } else if (bd.kind == OSOT_BOUND_JOINT_LIMITS_INVARIANCE) {
+                    const Box1 bx = invariance_bound(bd, bp, inst, n, i);
+                    l2 = bx.l; u2 = bx.u;
                 } else { l2 = bp.p0[inst * n + i]; u2 = bp.p1[inst * n + i]; }
                 if (j == 0) { l = l2; u = u2; } else { u = fmin(u, u2); l = fmax(l, l2); }
             }
@@ -1309,6 +1448,8 @@ __device__ __forceinline__ void update_body(const DevUpdate* args_global, const 
             for (int r = t; r < rb.rows; r += 64) { lob[r] = -1.0e20; upb[r] = 0.0; }
         } else if (rb.kind == OSOT_ROWS_CONVEX_HULL) {   // velocity::ConvexHull: the collision block's scratch holds the points
             convex_hull_rows(rb, rp, inst, n, t, Cb, lob, upb, dcand);
+        } else if (rb.kind >= OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY) {   // 18 .. 21: ONE call site (see limit_kind_rows)
+            limit_kind_rows(rb, rp, inst, n, t, Cb, lob, upb);
         } else if (rb.kind == 5) {   // acceleration::JointLimits (constraints/acceleration/JointLimits.cpp:58-176)
             const int nr = rb.rows;
             const double dt = rb.dT * rb.p;

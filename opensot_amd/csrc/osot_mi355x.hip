@@ -1228,6 +1228,8 @@ int osot_control_rollout(osot_solver* s, osot_kin* k, const osot_kin_batch* kb, 
     if (s && s->wide) return refuse_wide(s, "the fused control cycle / rollout");
     if (steps < 1) return fail(OSOT_ERR_INVALID, "a rollout has at least one step");
     if (steps > 1 && !q_integrate) return fail(OSOT_ERR_INVALID, "a rollout of several steps integrates q (q_integrate is null: every step would solve the same problem)");
+    if (s && steps > 1 && plan_has_invariance_bound(s->plan))
+        return fail(OSOT_ERR_UNSUPPORTED, "a rollout of several steps cannot carry OSOT_BOUND_JOINT_LIMITS_INVARIANCE: its qdot_prev leaf is not advanced inside a launch (use osot_control_cycle per step)");
     return control_launch(s, k, kb, leaf, out, b, q_integrate, steps, dq_steps, status_steps, hip_stream);
 }
 

@@ -57,7 +57,14 @@ inline int plan_constraint_rows(const osot_plan_desc* p, int* nc) {
 }
 
 inline bool rows_are_implicit(int kind) {
-    return kind == OSOT_ROWS_ACC_JOINT_LIMITS || kind == OSOT_ROWS_ACC_VELOCITY_LIMITS || kind == OSOT_ROWS_UNIT_GENERIC;
+    return kind == OSOT_ROWS_ACC_JOINT_LIMITS || kind == OSOT_ROWS_ACC_VELOCITY_LIMITS || kind == OSOT_ROWS_UNIT_GENERIC ||
+           kind == OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY || kind == OSOT_ROWS_ACC_JOINT_LIMITS_ECBF;
+}
+// the plan holds a bound whose leaf is the PREVIOUS cycle's velocity (velocity::JointLimitsInvariance): a rollout of several steps
+// cannot carry it, the leaf inputs are held fixed inside a launch
+inline bool plan_has_invariance_bound(const osot_plan_desc& p) {
+    for (int j = 0; j < p.n_bounds; ++j) if (p.bound[j].kind == OSOT_BOUND_JOINT_LIMITS_INVARIANCE) return true;
+    return false;
 }
 // every constraint row of the plan is an EQUALITY by construction: TaskToConstraint blocks (`stack << l_sole`,
 // TaskToConstraint.cpp:34-52) whose error band is a point -- the update writes lo = b + err_lb and up = b + err_ub, bit-equal
@@ -152,11 +159,22 @@ inline int plan_validate(const osot_plan_desc* p, const char** why, int wide = 0
         for (int k = 0; k < p->n_levels; ++k) for (int j = 0; j < p->level[k].n_tasks; ++j) rows_total += p->level[k].task[j].rows;
         if (rows_total > OSOT_KMAX_FLAT_ROWS) { *why = "more than 256 task rows in all levels together"; return OSOT_ERR_UNSUPPORTED; }
     }
-    for (int j = 0; j < p->n_bounds; ++j)
-        if (p->bound[j].kind < 0 || p->bound[j].kind > OSOT_BOUND_VELOCITY_LIMITS) { *why = "unknown bound kind"; return OSOT_ERR_UNSUPPORTED; }
+    for (int j = 0; j < p->n_bounds; ++j) {
+        const osot_bound_desc& bd = p->bound[j];
+        if (bd.kind < 0 || bd.kind > OSOT_BOUND_JOINT_LIMITS_INVARIANCE) { *why = "unknown bound kind"; return OSOT_ERR_UNSUPPORTED; }
+        if (bd.kind == OSOT_BOUND_JOINT_LIMITS_INVARIANCE && !(bd.dT > 0.0)) {
+            *why = "joint limits invariance: dT (the control period) must be positive"; return OSOT_ERR_INVALID; }
+        if (bd.kind == OSOT_BOUND_JOINT_LIMITS_INVARIANCE && !(bd.scaling > 0.0 && bd.scaling <= 1.0)) {   // setPStepAheadPredictor: p <= 1
+            *why = "joint limits invariance: scaling (the step-ahead predictor p) must be in (0, 1]"; return OSOT_ERR_INVALID; }
+    }
     for (int j = 0; j < p->n_rowblocks; ++j) {
         const osot_rows_desc& rb = p->rowblock[j];
-        if ((rb.kind < 0 || rb.kind > OSOT_ROWS_NORMAL_TORQUE) && rb.kind != OSOT_ROWS_CONVEX_HULL) { *why = "unknown row-block kind"; return OSOT_ERR_UNSUPPORTED; }
+        if ((rb.kind < 0 || rb.kind > OSOT_ROWS_NORMAL_TORQUE) && rb.kind != OSOT_ROWS_CONVEX_HULL &&
+            (rb.kind < OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY || rb.kind > OSOT_ROWS_POSITION_COM)) { *why = "unknown row-block kind"; return OSOT_ERR_UNSUPPORTED; }
+        if ((rb.kind == OSOT_ROWS_POSITION_CARTESIAN || rb.kind == OSOT_ROWS_POSITION_COM) && (rb.rows < 1 || rb.rows > 16)) {
+            *why = "Cartesian position constraint: rows = half-spaces, 1..16"; return OSOT_ERR_INVALID; }
+        if (rb.kind == OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY && !(rb.p >= 1.0)) {
+            *why = "viability joint limits: p (the step-ahead predictor) must be at least 1"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_CONVEX_HULL && (rb.rows < 3 || rb.rows > OSOT_KIN_MAX_POINTS)) {
             *why = "convex hull block: rows = contact points, 3..16"; return OSOT_ERR_INVALID; }
         if (rb.kind == OSOT_ROWS_TASK_CARTESIAN && rb.rows != 6) { *why = "a Cartesian task as a constraint has 6 rows"; return OSOT_ERR_INVALID; }
@@ -181,7 +199,7 @@ inline int plan_validate(const osot_plan_desc* p, const char** why, int wide = 0
         }
         if (rows_are_implicit(rb.kind) && (rb.first_col < 0 || rb.first_col + rb.rows > p->n)) {
             *why = "unit-row block exceeds the variables"; return OSOT_ERR_INVALID; }
-        if (rows_are_implicit(rb.kind) && rb.kind != OSOT_ROWS_UNIT_GENERIC && !(rb.dT * rb.p > 0.0)) { *why = "acceleration limits need dT*p > 0"; return OSOT_ERR_INVALID; }
+        if (rows_are_implicit(rb.kind) && rb.kind != OSOT_ROWS_UNIT_GENERIC && rb.kind != OSOT_ROWS_ACC_JOINT_LIMITS_ECBF && !(rb.dT * rb.p > 0.0)) { *why = "acceleration limits need dT*p > 0"; return OSOT_ERR_INVALID; }
         if (rb.only_level < 0 || rb.only_level > p->n_levels) { *why = "row block: only_level out of range (0..n_levels)"; return OSOT_ERR_INVALID; }
     }
     if (wide) {   // the workgroup solver's row limit (osot_qp_big.h: kMaxRows) holds the global rows and every level's optimality rows

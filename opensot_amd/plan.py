@@ -68,14 +68,15 @@ def subtask(parent: "Task", indices, lam=1.0, n=None) -> "Task":
 
 
 IMPLICIT_IDENTITY_TASKS = (abi.TASK_POSTURAL, abi.TASK_ACC_POSTURAL)
-UNIT_ROW_BLOCKS = (abi.ROWS_ACC_JOINT_LIMITS, abi.ROWS_ACC_VELOCITY_LIMITS, abi.ROWS_UNIT_GENERIC)
+UNIT_ROW_BLOCKS = (abi.ROWS_ACC_JOINT_LIMITS, abi.ROWS_ACC_VELOCITY_LIMITS, abi.ROWS_UNIT_GENERIC,
+                   abi.ROWS_ACC_JOINT_LIMITS_VIABILITY, abi.ROWS_ACC_JOINT_LIMITS_ECBF)
 
 
 @dataclass
 class Bound:
     kind: int
-    scaling: float = 1.0
-    dT: float = 0.0
+    scaling: float = 1.0   # BOUND_JOINT_LIMITS_INVARIANCE: the step-ahead predictor p (0 < p <= 1)
+    dT: float = 0.0        # BOUND_JOINT_LIMITS_INVARIANCE: the control period dt
     name: str = ""
 
 
@@ -85,11 +86,12 @@ class Rows:
     rows: int
     d_threshold: float = 0.0
     detection_threshold: float = 0.0
-    bound_scaling: float = 1.0   # ROWS_CONVEX_HULL: the safety margin in metres (ConvexHull::setSafetyMargin)
+    # ROWS_CONVEX_HULL: the safety margin in metres (ConvexHull::setSafetyMargin); ROWS_POSITION_*: CartesianPositionConstraint's boundScaling
+    bound_scaling: float = 1.0
     name: str = ""
     first_col: int = 0
     dT: float = 0.0
-    p: float = 1.0
+    p: float = 1.0            # ROWS_ACC_JOINT_LIMITS_VIABILITY: the step-ahead predictor, p >= 1; ROWS_ACC_JOINT_LIMITS_ECBF: not read
     mu: float = 0.0
     # None: global rows (every level).  k: task-local rows of level k (`task << constraint`, Task::getConstraints(),
     # iHQP.cpp:190, 282-287): they constrain level k's QP only
@@ -177,6 +179,15 @@ class StackPlan:
         for r in self.rowblocks:
             if r.kind == abi.ROWS_CONVEX_HULL:   # rows = contact points = the fixed row count (stored rows: not in UNIT_ROW_BLOCKS)
                 assert 3 <= r.rows <= abi.KIN_MAX_POINTS, "convex hull block: 3 .. 16 contact points"
+            if r.kind in (abi.ROWS_POSITION_CARTESIAN, abi.ROWS_POSITION_COM):   # rows = half-spaces; stored rows
+                assert 1 <= r.rows <= abi.MAX_POSITION_ROWS, "Cartesian position constraint: 1 .. 16 half-spaces"
+            if r.kind == abi.ROWS_ACC_JOINT_LIMITS_VIABILITY:
+                assert r.p >= 1.0 and r.dT * r.p > 0.0, "viability joint limits: p >= 1 and dT > 0"
+            if r.kind in (abi.ROWS_ACC_JOINT_LIMITS_VIABILITY, abi.ROWS_ACC_JOINT_LIMITS_ECBF):
+                assert r.first_col >= 0 and r.first_col + r.rows <= self.n
+        for b in self.bounds:
+            if b.kind == abi.BOUND_JOINT_LIMITS_INVARIANCE:
+                assert 0.0 < b.scaling <= 1.0 and b.dT > 0.0, "joint limits invariance: 0 < p <= 1 and dt > 0"
         if self.regularisation is not None:
             r = self.regularisation
             assert not r.row_mask

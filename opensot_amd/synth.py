@@ -813,3 +813,204 @@ def bind_balance(stack, kin, leaf):
     dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
     dev["rows"][0] = (stack.A[0], com, pts)
     return dev, kin.batch_args(q, **kw), q
+
+
+# ---- the recursively feasible joint limits, the Cartesian position constraint, CartesianVelocity ----------------------------------
+def near_limit_states(rng, B, n, qmin, qmax, amax):
+    """i.i.d. states that exercise the joint-limit kinds where a closed loop does not go (the swap branch of ECBF): q within
+    10^U(-4, -1) of a limit (upper or lower with equal odds), qdot ~ N(0, 1) sqrt(2 amax gap) -- velocities of the size that just
+    stops inside the gap.  -> q, qdot [B][n]"""
+    gap = 10.0 ** rng.uniform(-4.0, -1.0, size=(B, n))
+    upper = rng.random((B, n)) < 0.5
+    q = np.where(upper, qmax - gap, qmin + gap)
+    qdot = rng.normal(size=(B, n)) * np.sqrt(2.0 * amax * gap)
+    return q, qdot
+
+
+def make_viability_stack(B, n, kind=abi.ROWS_ACC_JOINT_LIMITS_VIABILITY, seed=None, dT=0.01, p=1.0, qdot_max=2.0, qddot_max=12.0,
+                         alpha=15.0, lam=400.0, first_col=0, rows=None, eps_factor=1e6):
+    """`postural << joint_limits` of the reference's closed-loop joint-limit tests (tests/constraints/acceleration/
+    TestJointLimitsViability.cpp, TestJointLimitsECBF.cpp) without a robot: one level, acceleration::Postural (lambda, lambda2 =
+    2 sqrt(lambda)) on all n coordinates, under ONE block of `kind` (ROWS_ACC_JOINT_LIMITS_VIABILITY with the step-ahead predictor p,
+    or ROWS_ACC_JOINT_LIMITS_ECBF with a1 = a2 = a3 = alpha) on the coordinates first_col .. first_col + rows - 1 (default: all).
+    Limits +-U(0.5, 2.5); the start is the middle of the range, at rest.  The leaf's q is q - q_neutral with a zero neutral
+    posture (see OSOT_ROWS_ACC_JOINT_LIMITS_VIABILITY in the header for the convention).
+    leaf["state"]: q, qdot [B][n], qmin, qmax [B][rows]; set_viability_state() writes a state into the leaf in place."""
+    assert kind in (abi.ROWS_ACC_JOINT_LIMITS_VIABILITY, abi.ROWS_ACC_JOINT_LIMITS_ECBF)
+    rng = np.random.default_rng(13000 if seed is None else seed)
+    rows = n - first_col if rows is None else rows
+    half = rng.uniform(0.5, 2.5, size=(B, rows))
+    qmin, qmax = -half, half
+    q, qdot = np.zeros((B, n)), np.zeros((B, n))
+    q[:, first_col:first_col + rows] = 0.5 * (qmin + qmax)
+    lim = [np.full((B, rows), qdot_max), np.full((B, rows), qddot_max)]
+    if kind == abi.ROWS_ACC_JOINT_LIMITS_ECBF:
+        lim += [np.full((B, rows), float(alpha))] * 3
+    levels = [[Task(abi.TASK_ACC_POSTURAL, n, lam=lam, lam2=2.0 * np.sqrt(lam), name="postural")]]
+    rowblocks = [Rows(kind, rows, first_col=first_col, dT=dT, p=p, name="joint_limits")]
+    plan = StackPlan(n=n, levels=levels, bounds=[], rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [None], "task": [[(np.zeros((B, 2 * n)), None, None)]], "bound": [],
+            "rows": [(np.zeros((B, 2 * rows)), np.concatenate([qmin, qmax], axis=1), np.concatenate(lim, axis=1))], "C": [None],
+            "state": {"q": q, "qdot": qdot, "qmin": qmin, "qmax": qmax}}
+    set_viability_state(plan, leaf, q, qdot, q)
+    return plan, leaf
+
+
+def set_viability_state(plan, leaf, q, qdot, q_ref):
+    """write the state (q, qdot [B][n]) and the posture reference q_ref [B][n] into the leaf arrays of make_viability_stack, in place:
+    the Postural task's [q_ref - q ; -qdot] and the limit block's [q ; qdot] on its columns"""
+    n, rb = plan.n, plan.rowblocks[0]
+    c0, r = rb.first_col, rb.rows
+    t0 = leaf["task"][0][0][0]
+    t0[:, :n] = q_ref - q
+    t0[:, n:] = -qdot
+    r0 = leaf["rows"][0][0]
+    r0[:, :r] = q[:, c0:c0 + r]
+    r0[:, r:] = qdot[:, c0:c0 + r]
+
+
+def make_invariance_stack(B, n, seed=None, dt=1e-3, p=0.9, qdot_max=2.0, qddot_max=20.0, lam=0.1, eps_factor=1e6):
+    """`postural << velocity_limits << joint_limits_invariance` of the reference's tests/constraints/velocity/
+    TestJointLimitsInvariance.cpp without a robot: velocity::Postural (lambda) under BOUND_VELOCITY_LIMITS (qdot_max, dT = dt) and
+    BOUND_JOINT_LIMITS_INVARIANCE (qddot_max, dt, the step-ahead predictor p).  Limits +-U(0.5, 2.5); the start is the middle of the
+    range, at rest.  Per cycle the caller integrates q += dq and writes qdot_prev = dq / dt into the bound's leaf p2.
+    leaf["state"]: q, qmin, qmax [B][n]."""
+    rng = np.random.default_rng(14000 if seed is None else seed)
+    half = rng.uniform(0.5, 2.5, size=(B, n))
+    qmin, qmax = -half, half
+    q = 0.5 * (qmin + qmax)
+    levels = [[Task(abi.TASK_POSTURAL, n, lam=lam, name="postural")]]
+    bounds = [Bound(abi.BOUND_VELOCITY_LIMITS, dT=dt, name="velocity_limits"),
+              Bound(abi.BOUND_JOINT_LIMITS_INVARIANCE, scaling=p, dT=dt, name="joint_limits_invariance")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, rowblocks=[], eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [None], "task": [[(q.copy(), q.copy(), None)]],
+            "bound": [(np.full((B, n), qdot_max), None, None),
+                      (q.copy(), np.concatenate([qmin, qmax, np.full((B, n), qddot_max)], axis=1), np.zeros((B, n)))],
+            "rows": [], "C": [], "state": {"q": q, "qmin": qmin, "qmax": qmax}}
+    return plan, leaf
+
+
+def make_position_stack(B, n, R, seed=None, kind=abi.ROWS_POSITION_CARTESIAN, bound_scaling=1.0, eps_factor=1e6):
+    """A velocity stack under the reference's workspace constraint, `(task / postural) << joint_limits << velocity_limits <<
+    position_constraint` (constraints::velocity::CartesianPositionConstraint, CartesianPositionConstraint.cpp:81-108):
+
+    levels : 0 = velocity::Cartesian on a link (ROWS_POSITION_CARTESIAN) or velocity::CoM (ROWS_POSITION_COM); its Jacobian A_0 is
+             the position block's leaf p0 (one [B][6][n] / [B][3][n] array), its actual pose / CoM the block's p1;  1 = Postural
+    box    : joint limits, velocity limits
+    rows   : R half-spaces A_c x <= b_c on the link's / the CoM's position
+
+    Model quantities are synthetic (J ~ N(0, 0.3^2), a random pose).  Half-space 0 has the direction of the task's position error as its
+    normal; in every second instance it lies 30 % of the way to where the task's gain would take the position in one step, so the
+    unconstrained optimum violates it; elsewhere it lies beyond the reference.  The others are random planes 0.05 .. 0.2 m away."""
+    assert kind in (abi.ROWS_POSITION_CARTESIAN, abi.ROWS_POSITION_COM) and 1 <= R <= abi.MAX_POSITION_ROWS
+    rng = np.random.default_rng(15000 if seed is None else seed)
+    cart = kind == abi.ROWS_POSITION_CARTESIAN
+    lam = 0.1
+    bounds, bleaf = _box_leaf(rng, B, n, jl=True, vl=True)
+    mt = 6 if cart else 3
+    J = rng.normal(0.0, 0.3, size=(B, mt, n))
+    if cart:
+        Ta, Td, _ = _cartesian_leaf(rng, B)
+        x, xd = Ta[:, 9:], Td[:, 9:]
+        task, tl = Task(abi.TASK_CARTESIAN, 6, lam=lam, name="link"), (Ta, Td, None)
+    else:
+        x = rng.uniform(-0.2, 0.2, size=(B, 3))
+        dp = rng.normal(size=(B, 3))
+        xd = x + dp * (rng.uniform(0.02, 0.05, size=(B, 1)) / np.linalg.norm(dp, axis=1, keepdims=True))
+        task, tl = Task(abi.TASK_COM, 3, lam=lam, name="com"), (x, xd, None)
+    Ac = rng.normal(size=(B, R, 3))
+    Ac /= np.linalg.norm(Ac, axis=2, keepdims=True)
+    bc = np.einsum("brk,bk->br", Ac, x) + rng.uniform(0.05, 0.2, size=(B, R))
+    e = xd - x
+    dist = np.linalg.norm(e, axis=1)
+    Ac[:, 0] = e / dist[:, None]
+    frac = np.where(np.arange(B) % 2 == 0, 0.3, 20.0)
+    bc[:, 0] = np.einsum("bk,bk->b", Ac[:, 0], x) + frac * lam * dist / bound_scaling
+    q = bleaf[0][0]
+    levels = [[task], [Task(abi.TASK_POSTURAL, n, lam=0.01, name="postural")]]
+    tleaf = [[tl], [(q, q + rng.normal(0.0, 0.1, size=(B, n)), None)]]
+    rowblocks = [Rows(kind, R, bound_scaling=bound_scaling, name="position_constraint")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    p2 = np.concatenate([Ac.reshape(B, 3 * R), bc], axis=1)
+    leaf = {"B": B, "A": [J, None], "task": tleaf, "bound": bleaf, "rows": [(J, tl[0], p2)], "C": [None]}
+    return plan, leaf
+
+
+def make_coman_position_stack(B, seed=None, tree=None, frame="l_wrist", plane=0.1, beyond=0.3, bound_scaling=0.5, eps_factor=1e6):
+    """`(l_wrist / postural) << joint_limits << velocity_limits << position_constraint` on the reference's COMAN (35 coordinates) with the
+    hand's pose and Jacobian LEFT FOR THE KINEMATICS PRODUCER: the Jacobian goes into A_0, which is also the position block's leaf p0
+    (level 0 holds the hand's task alone, so A_0 is the dense [B][6][n] array the block reads), the pose into the task's p0, which is
+    also the block's p1.  A frame whose task SHARES its level with other tasks has its Jacobian rows inside a wider A_k (row stride
+    ma_k n): the block cannot read those, so such a frame is declared a second time in the model (osot_kin_desc), its second frame_J
+    pointing at a dense [B][6][n] leaf buffer of its own.
+    One half-space: a plane `plane` metres ahead of the hand, normal to a per-instance horizontal direction; the hand's reference lies
+    `beyond` metres past it.  Returns (plan, leaf, model); leaf["state"] = q0, q_ref, normal [B][3].  bind_position() wires the device
+    tensors."""
+    import os
+    from . import kinematics as kin
+    here = os.path.dirname(os.path.abspath(__file__))
+    model, lo, up = kin.from_json(tree or os.path.join(os.path.dirname(here), "tests", "golden", "coman_tree.json"))
+    rng = np.random.default_rng(16000 if seed is None else seed)
+    n = model.n
+    ix = model.names.index
+    q0 = np.zeros((B, n))
+    for s_ in "LR":
+        q0[:, ix(s_ + "HipSag")] = -0.3; q0[:, ix(s_ + "KneeSag")] = 0.6; q0[:, ix(s_ + "AnkSag")] = -0.3
+        q0[:, ix(s_ + "Elbj")] = -0.8; q0[:, ix(s_ + "ShSag")] = 0.2
+    q0[:, ix("LShLat")] = 0.3; q0[:, ix("RShLat")] = -0.3
+    q0[:, 6:] += rng.normal(0.0, 0.02, (B, n - 6))
+    qmin, qmax = np.maximum(lo, -10.0), np.minimum(up, 10.0)
+    q0 = np.clip(q0, qmin + 1e-3, qmax - 1e-3)
+    q_ref = q0.copy()
+    ang = rng.uniform(-0.5, 0.5, size=(B, 1))                     # ahead of the robot, up to half a radian to either side
+    normal = np.concatenate([np.cos(ang), np.sin(ang), np.zeros((B, 1))], axis=1)
+    z = lambda *sh: np.zeros(sh)
+    levels = [[Task(abi.TASK_CARTESIAN, 6, lam=0.1, name=frame)], [Task(abi.TASK_POSTURAL, n, lam=0.01, name="postural")]]
+    bounds = [Bound(abi.BOUND_JOINT_LIMITS, scaling=1.0, name="joint_limits"), Bound(abi.BOUND_VELOCITY_LIMITS, dT=0.05, name="velocity_limits")]
+    rowblocks = [Rows(abi.ROWS_POSITION_CARTESIAN, 1, bound_scaling=bound_scaling, name="position_constraint")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, 6, n), None], "task": [[(z(B, 12), z(B, 12), None)], [(q0.copy(), q_ref, None)]],
+            "bound": [(q0.copy(), np.tile(qmin, (B, 1)), np.tile(qmax, (B, 1))), (np.full((B, n), 2.0), None, None)],
+            "rows": [(z(B, 6, n), z(B, 12), np.concatenate([normal, z(B, 1)], axis=1))], "C": [None],
+            "state": {"q0": q0, "q_ref": q_ref, "normal": normal, "frame": frame, "plane": plane, "beyond": beyond}}
+    return plan, leaf, model
+
+
+def bind_position(stack, kin, leaf):
+    """wire make_coman_position_stack to the device: one q tensor is the producer's input, the Postural task's and the joint limits' q
+    (and what q_integrate advances); the producer writes the hand's pose into the Cartesian task's p0 (= the position block's p1) and its
+    Jacobian into stack.A[0] (= the block's p0).  The plane lies leaf["state"]["plane"] metres ahead of the first posture's hand along
+    the instance's normal, the hand's reference "beyond" metres past it, with the first posture's orientation.
+    -> (dev_leaf, kin_batch, q)"""
+    import torch
+    B, s = leaf["B"], leaf["state"]
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q = torch.as_tensor(s["q0"], **f64).contiguous()
+    f = kin.model.frame_index(s["frame"])
+    pose = torch.zeros((B, 12), **f64)
+    kw = dict(frame_pose={f: pose}, frame_J={f: (stack.A[0], 0)})
+    kin.forward(q, **kw)
+    nrm = torch.as_tensor(s["normal"], **f64)
+    ref = pose.clone()
+    ref[:, 9:] += (s["plane"] + s["beyond"]) * nrm
+    p2 = torch.cat([nrm, (nrm * pose[:, 9:]).sum(dim=1, keepdim=True) + s["plane"]], dim=1).contiguous()
+    dev["task"][0][0] = (pose, ref, None)
+    dev["task"][1][0] = (q, dev["task"][1][0][1], None)
+    dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
+    dev["rows"][0] = (stack.A[0], pose, p2)
+    return dev, kin.batch_args(q, **kw), q
+
+
+def cartesian_velocity_rows(task_kind, v_lim, dT, name="cartesian_velocity"):
+    """constraints::velocity::CartesianVelocity (src/constraints/velocity/CartesianVelocity.cpp:77-96; `comVelocity` of the reference's
+    DefaultHumanoidStack): -v_lim dT <= J dq <= v_lim dT on the linear velocity of the CoM or of a link.  It needs no kind of its own: it
+    is the task used as a constraint (constraints::TaskToConstraint) with lambda = 0 -- so b = 0 whatever the pose error -- and the
+    error band +-v_lim dT.  task_kind: ROWS_TASK_COM (3 rows; v_lim a scalar or 3 values) or ROWS_TASK_CARTESIAN (6 rows; v_lim a
+    scalar or 6 values: the reference bounds the three linear rows only, so pass a large value for the angular ones).  The leaf is the
+    task's own (actual and desired pose / CoM; the desired one is not felt at lambda = 0, p2 = NULL); the producer writes J into C."""
+    assert task_kind in (abi.ROWS_TASK_COM, abi.ROWS_TASK_CARTESIAN)
+    rows = 3 if task_kind == abi.ROWS_TASK_COM else 6
+    band = np.broadcast_to(np.asarray(v_lim, dtype=float), (rows,)) * float(dT)
+    assert (band >= 0.0).all()
+    return Rows(task_kind, rows, lam=0.0, orientation_gain=1.0, err_lb=(-band).tolist(), err_ub=band.tolist(), name=name)
