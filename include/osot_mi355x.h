@@ -825,6 +825,50 @@ int osot_dyn_destroy(osot_dyn* d);
  * (OSOT_ERR_UNSUPPORTED; the reference leaves the relative case open as well, acceleration/Cartesian.cpp:144). */
 int osot_dynamics(osot_dyn* d, const osot_dyn_batch* batch, void* hip_stream);
 
+/* ---- batched posture-gradient producer ---------------------------------------------------------------------------
+ * The b of tasks::velocity::Manipulability (Manipulability.cpp:58-84) and tasks::velocity::MinimumEffort (MinimumEffort.cpp:51-77)
+ * for the tree of an osot_kin_desc.  Per term and ACTIVE joint i, in the reference's order:
+ *     grad[i] = (f(q + step e_i) - f(q - step e_i)) / (2 step),   0 for a joint that is not active
+ *     b = lambda grad (manipulability),   b = -1.0 lambda grad (minimum effort)
+ *     manipulability: f = sqrt(fabs(det(J W J'))), J = the 6 x n Jacobian of a frame (world, or relative to its frame_base), or the
+ *                     3 x n Jacobian of the centre of mass (Manipulability.h:130-150)
+ *     minimum effort: f = tau_g' W tau_g, tau_g = the gravity compensation over all n coordinates (MinimumEffort.h:89-96)
+ * q + delta is plain addition: the floating base of this project is three prismatic and three revolute virtual joints.
+ *   - The worker builds a FRESH Cartesian task on its own model copy, so frame_col_mask of the osot_kin_desc is NOT applied to J.
+ *   - frame_body and the R_b' rotation of a relative Jacobian are orthogonal block transforms of J: the determinant does not see
+ *     them, and the kernel skips them.
+ *   - tau_g = -M_tot J_com' g, which is what osot_dynamics writes as h when qdot is NULL.
+ * W is the worker's CONSTANT weight (setW); only its diagonal is offered (a dense W is not).  The tasks themselves have A = I, W = I:
+ * b goes into the leaf of an implicit OSOT_TASK_POSTURAL block (p1 = p0, p2 = b) or of an OSOT_TASK_GENERIC block with stored unit
+ * rows, by its own launch in front of osot_cycle / osot_control_cycle. */
+enum { OSOT_GRAD_MANIPULABILITY_FRAME = 0, OSOT_GRAD_MANIPULABILITY_COM = 1, OSOT_GRAD_MIN_EFFORT = 2 };
+#define OSOT_GRAD_MAX_TERMS 4
+typedef struct {
+    int n_terms;                                           /* 1 .. OSOT_GRAD_MAX_TERMS                                          */
+    int kind[OSOT_GRAD_MAX_TERMS];
+    int frame[OSOT_GRAD_MAX_TERMS];                        /* MANIPULABILITY_FRAME: a frame of the tree; its frame_base is honoured */
+    double step[OSOT_GRAD_MAX_TERMS];                      /* finite, > 0; the reference's default is 1e-3                      */
+    double lambda[OSOT_GRAD_MAX_TERMS];
+    unsigned long long joint_mask[OSOT_GRAD_MAX_TERMS];    /* Task::getActiveJointsMask: bit i CLEAR = grad[i] is 0; 0 = all active */
+    double W_diag[OSOT_GRAD_MAX_TERMS][OSOT_KIN_MAX_JOINTS]; /* diagonal of the worker's weight, one entry per coordinate        */
+    double gravity[3];                                     /* world frame, e.g. (0, 0, -9.81)                                   */
+} osot_grad_desc;
+typedef struct {
+    int B;
+    const double* q;                                       /* [B][n]                                                            */
+    double* b[OSOT_GRAD_MAX_TERMS];                        /* first of the n entries of instance 0, or NULL (then stride 0)     */
+    long long b_stride[OSOT_GRAD_MAX_TERMS];               /* doubles from one instance to the next (>= n)                      */
+    double* value[OSOT_GRAD_MAX_TERMS];                    /* [B]: ComputeManipulabilityIndex() / computeEffort() at q, or NULL */
+} osot_grad_batch;
+typedef struct osot_grad osot_grad;
+/* Refused with OSOT_ERR_INVALID before any device is touched: what osot_dyn_create refuses of a tree, n_terms outside 1 .. 4, an
+ * unknown kind, a frame out of range, a step that is not finite or not > 0, a lambda, W_diag or gravity that is not finite. */
+int osot_grad_create(const osot_kin_desc* tree, const osot_grad_desc* desc, int device, osot_grad** out);
+int osot_grad_destroy(osot_grad* g);
+/* Stream-ordered, no allocation, capturable.  OSOT_ERR_INVALID: B < 0, q NULL, a NULL b with a stride, a stride below n, an output
+ * bound to a term beyond n_terms.  B == 0 is a no-op. */
+int osot_posture_gradient(osot_grad* g, const osot_grad_batch* batch, void* hip_stream);
+
 /* ---- layout of the structs above as THIS library was compiled (for bindings that mirror them by hand: ctypes, cgo, JNI ...).
  * name = the typedef's name ("osot_plan_desc", "osot_qp_batch", ...).  *size = sizeof; the byte offset of every member, in
  * declaration order, goes to offsets[0 .. *n_fields) (at most max_fields are written; offsets may be NULL).  Unknown name:

@@ -165,13 +165,30 @@ class DynBatch(C.Structure):
                 ("com_Jdot_qdot", C.c_void_p), ("com_Jdot_qdot_stride", C.c_longlong)]
 
 
+GRAD_MANIPULABILITY_FRAME, GRAD_MANIPULABILITY_COM, GRAD_MIN_EFFORT = range(3)
+GRAD_MAX_TERMS = 4
+
+
+class GradDesc(C.Structure):
+    _fields_ = [("n_terms", C.c_int), ("kind", C.c_int * GRAD_MAX_TERMS), ("frame", C.c_int * GRAD_MAX_TERMS),
+                ("step", C.c_double * GRAD_MAX_TERMS), ("lambda_", C.c_double * GRAD_MAX_TERMS),
+                ("joint_mask", C.c_ulonglong * GRAD_MAX_TERMS), ("W_diag", (C.c_double * KIN_MAX_JOINTS) * GRAD_MAX_TERMS),
+                ("gravity", C.c_double * 3)]
+
+
+class GradBatch(C.Structure):
+    _fields_ = [("B", C.c_int), ("q", C.c_void_p), ("b", C.c_void_p * GRAD_MAX_TERMS), ("b_stride", C.c_longlong * GRAD_MAX_TERMS),
+                ("value", C.c_void_p * GRAD_MAX_TERMS)]
+
+
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
     "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
-    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
+    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
+    "osot_grad_create", "osot_grad_destroy", "osot_posture_gradient", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
     "osot_backend_create", "osot_backend_destroy", "osot_backend_init_problem",
     "osot_backend_update_task", "osot_backend_update_constraints", "osot_backend_update_bounds",
     "osot_backend_solve", "osot_backend_get_solution", "osot_backend_get_objective",
@@ -188,7 +205,7 @@ STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound
            "osot_plan_desc": PlanDesc, "osot_qp_batch": QpBatch, "osot_leaf_ptrs": LeafPtrs, "osot_leaf_batch": LeafBatch,
            "osot_assembled_out": AssembledOut, "osot_backend_options": BackendOptions, "osot_nhqp_options": NhqpOptions,
            "osot_admm_options": AdmmOptions, "osot_id_model": IdModel, "osot_kin_desc": KinDesc, "osot_kin_batch": KinBatch,
-           "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch}
+           "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -247,6 +264,9 @@ def lib():
     L.osot_dyn_create.argtypes = [C.POINTER(KinDesc), C.POINTER(DynDesc), C.c_int, C.POINTER(vp)]
     L.osot_dyn_destroy.argtypes = [vp]
     L.osot_dynamics.argtypes = [vp, C.POINTER(DynBatch), vp]
+    L.osot_grad_create.argtypes = [C.POINTER(KinDesc), C.POINTER(GradDesc), C.c_int, C.POINTER(vp)]
+    L.osot_grad_destroy.argtypes = [vp]
+    L.osot_posture_gradient.argtypes = [vp, C.POINTER(GradBatch), vp]
     L.osot_control_cycle.argtypes = [vp, vp, C.POINTER(KinBatch), C.POINTER(LeafBatch), C.POINTER(AssembledOut), C.POINTER(QpBatch), vp, vp]
     L.osot_control_rollout.argtypes = [vp, vp, C.POINTER(KinBatch), C.POINTER(LeafBatch), C.POINTER(AssembledOut), C.POINTER(QpBatch), vp, C.c_int, vp, vp, vp]
     L.osot_solver_profile_phases.argtypes = [vp, C.POINTER(QpBatch), vp, vp]

@@ -18,6 +18,7 @@
 #include "osot_host_plan.h"
 #include "osot_kin.h"
 #include "osot_dyn.h"
+#include "osot_grad.h"
 #include "osot_control.h"
 #include "osot_ehqp.h"
 #include "osot_id.h"
@@ -204,6 +205,9 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
     OSOT_LAYOUT_BEGIN(osot_dyn_desc) OSOT_F(inertia) OSOT_F(gravity) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_batch) OSOT_F(B) OSOT_F(q) OSOT_F(qdot) OSOT_F(M) OSOT_F(M_stride) OSOT_F(h) OSOT_F(frame_Jdot_qdot)
         OSOT_F(frame_Jdot_qdot_stride) OSOT_F(com_Jdot_qdot) OSOT_F(com_Jdot_qdot_stride) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_grad_desc) OSOT_F(n_terms) OSOT_F(kind) OSOT_F(frame) OSOT_F(step) OSOT_F(lambda) OSOT_F(joint_mask)
+        OSOT_F(W_diag) OSOT_F(gravity) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_grad_batch) OSOT_F(B) OSOT_F(q) OSOT_F(b) OSOT_F(b_stride) OSOT_F(value) OSOT_LAYOUT_END()
 #undef OSOT_LAYOUT_BEGIN
 #undef OSOT_F
 #undef OSOT_LAYOUT_END
@@ -1211,6 +1215,52 @@ int osot_dynamics(osot_dyn* d, const osot_dyn_batch* b, void* hip_stream) {
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
     hipLaunchKernelGGL((osot_dyn_kernel<64>), dim3((unsigned)b->B), dim3(64), 0, (hipStream_t)hip_stream, (const DevDyn*)d->dev, *b, dyn_kin_batch(*b));
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// batched posture-gradient producer (osot_grad.h): the b of velocity::Manipulability and velocity::MinimumEffort
+struct osot_grad {
+    DevGrad* dev;
+    int n, n_terms;
+    int device;
+};
+
+int osot_grad_create(const osot_kin_desc* tree, const osot_grad_desc* desc, int device, osot_grad** out) {
+    if (!tree || !desc || !out) return fail(OSOT_ERR_INVALID, "null argument");
+    std::vector<DevGrad> image(1);   // (not on the stack)
+    DevGrad& h = image[0];
+    const char* why = "";
+    const int rc = grad_build(tree, desc, h, &why);
+    if (rc != OSOT_OK) return fail(rc, why);
+    DeviceGuard guard(device);
+    if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    osot_grad* g = new osot_grad();
+    g->n = h.k.d.n; g->n_terms = h.n_terms; g->device = device; g->dev = nullptr;
+    hipError_t e = hipMalloc(&g->dev, sizeof(DevGrad));
+    if (e == hipSuccess) e = hipMemcpy(g->dev, &h, sizeof(DevGrad), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { if (g->dev) hipFree(g->dev); delete g; return fail(OSOT_ERR_HIP, hipGetErrorString(e)); }
+    *out = g;
+    return OSOT_OK;
+}
+
+int osot_grad_destroy(osot_grad* g) {
+    if (!g) return OSOT_OK;
+    DeviceGuard guard(g->device);
+    if (g->dev) hipFree(g->dev);
+    delete g;
+    return OSOT_OK;
+}
+
+int osot_posture_gradient(osot_grad* g, const osot_grad_batch* b, void* hip_stream) {
+    if (!g || !b) return fail(OSOT_ERR_INVALID, "null argument");
+    const char* why = "";
+    const int rc = grad_check_batch(g->n, g->n_terms, b, &why);
+    if (rc != OSOT_OK) return fail(rc, why);
+    if (b->B == 0) return OSOT_OK;
+    DeviceGuard guard(g->device);
+    if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    hipLaunchKernelGGL((osot_grad_kernel<64>), dim3((unsigned)b->B), dim3(64), 0, (hipStream_t)hip_stream, (const DevGrad*)g->dev, *b, grad_kin_batch(*b));
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

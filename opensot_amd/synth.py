@@ -1014,3 +1014,105 @@ def cartesian_velocity_rows(task_kind, v_lim, dT, name="cartesian_velocity"):
     band = np.broadcast_to(np.asarray(v_lim, dtype=float), (rows,)) * float(dT)
     assert (band >= 0.0).all()
     return Rows(task_kind, rows, lam=0.0, orientation_gain=1.0, err_lb=(-band).tolist(), err_ub=band.tolist(), name=name)
+
+
+# ---- velocity::MinimumEffort and velocity::Manipulability: the b comes from the posture-gradient producer ---------------------------
+def _coman_bent(rng, B, tree=None):
+    """the reference's COMAN from the tree fixture in a standing posture, knees and elbows bent: (model, q0 [B][n], q_min, q_max)"""
+    import os
+    from . import kinematics as kin
+    here = os.path.dirname(os.path.abspath(__file__))
+    model, lo, up = kin.from_json(tree or os.path.join(os.path.dirname(here), "tests", "golden", "coman_tree.json"))
+    n, ix = model.n, model.names.index
+    q0 = np.zeros((B, n))
+    for s_ in "LR":
+        q0[:, ix(s_ + "HipSag")] = -0.3; q0[:, ix(s_ + "KneeSag")] = 0.6; q0[:, ix(s_ + "AnkSag")] = -0.3
+        q0[:, ix(s_ + "Elbj")] = -0.8; q0[:, ix(s_ + "ShSag")] = 0.2
+    q0[:, ix("LShLat")] = 0.3; q0[:, ix("RShLat")] = -0.3
+    q0[:, 6:] += rng.normal(0.0, 0.02, (B, n - 6))
+    qmin, qmax = np.maximum(lo, -10.0), np.minimum(up, 10.0)
+    return model, np.clip(q0, qmin + 1e-3, qmax - 1e-3), qmin, qmax
+
+
+def make_min_effort_stack(B, seed=None, tree=None, w_scale=1e-5, lam=1.0, step=1e-3, eps_factor=1e6):
+    """tasks::velocity::MinimumEffort alone in a stack, as tests/tasks/velocity/TestMinimumEffort.cpp:80-104 builds it on COMAN: one level,
+    A = I, W = I, b = -lambda grad(tau_g' W_effort tau_g) with W_effort = w_scale I (the test sets 1e-5 I).  The task is an implicit
+    OSOT_TASK_POSTURAL block whose actual and reference posture are the SAME array (lambda (q - q) = 0) and whose feed-forward leaf p2
+    is the producer's output.  Returns (plan, leaf, model, terms): terms is the list for gradient.PostureGradient;
+    bind_posture_gradient() wires the device tensors."""
+    from .gradient import posture_term
+    rng = np.random.default_rng(17000 if seed is None else seed)
+    model, q0, _, _ = _coman_bent(rng, B, tree)
+    n = model.n
+    plan = StackPlan(n=n, levels=[[Task(abi.TASK_POSTURAL, n, lam=1.0, name="min_effort")]], eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [None], "task": [[(q0.copy(), q0.copy(), np.zeros((B, n)))]], "bound": [], "rows": [], "C": [],
+            "state": {"q0": q0, "gradient": [(0, 0, 0)]}}
+    terms = [posture_term(abi.GRAD_MIN_EFFORT, step=step, lam=lam, W=np.full(n, w_scale))]
+    return plan, leaf, model, terms
+
+
+def make_coman_manipulability_stack(B, seed=None, tree=None, lam=1.0, step=1e-3, postural_lam=0.1, dT=0.01, eps_factor=1e6):
+    """`((l_wrist + r_wrist) / (manipulability_l + manipulability_r + postural)) << joint_limits << velocity_limits` on the reference's
+    COMAN, after tests/tasks/velocity/TestManipulability.cpp:55-100: the two wrists are Cartesian tasks RELATIVE to the waist (a frame
+    "Waist" on the pelvis link is added to the model), the bottom level aggregates the two velocity::Manipulability tasks of those
+    Cartesian tasks with velocity::Postural.  The manipulability tasks (A = I) are OSOT_TASK_GENERIC blocks with stored unit rows --
+    the level also holds the implicit Postural block, which must be its last one -- and their b is the producer's output, written
+    straight into the blocks' leaf p0.  Poses and Jacobians of the wrists are left for the kinematics producer.
+    Returns (plan, leaf, model, terms); leaf["state"] = q0, q_ref; bind_posture_gradient() wires the device tensors."""
+    from .gradient import posture_term
+    rng = np.random.default_rng(18000 if seed is None else seed)
+    model, q0, qmin, qmax = _coman_bent(rng, B, tree)
+    n = model.n
+    model.frames = list(model.frames) + [("Waist", model.names.index("VIRTUALJOINT_6"), np.eye(3), (0.0, 0.0, 0.0))]
+    fl, fr, fw = model.frame_index("l_wrist"), model.frame_index("r_wrist"), model.frame_index("Waist")
+    model.frame_base = {fl: fw, fr: fw}
+    z = lambda *sh: np.zeros(sh)
+    levels = [[Task(abi.TASK_CARTESIAN, 6, lam=1.0, name="l_wrist"), Task(abi.TASK_CARTESIAN, 6, lam=1.0, name="r_wrist")],
+              [Task(abi.TASK_GENERIC, n, name="manipulability::l_wrist"), Task(abi.TASK_GENERIC, n, name="manipulability::r_wrist"),
+               Task(abi.TASK_POSTURAL, n, lam=postural_lam, name="postural")]]
+    bounds = [Bound(abi.BOUND_JOINT_LIMITS, scaling=0.2, name="joint_limits"), Bound(abi.BOUND_VELOCITY_LIMITS, dT=dT, name="velocity_limits")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, eps_abs=eps_abs_from_factor(eps_factor))
+    unit = np.tile(np.concatenate([np.eye(n), np.eye(n)], axis=0), (B, 1, 1))
+    leaf = {"B": B, "A": [z(B, 12, n), unit],
+            "task": [[(z(B, 12), z(B, 12), None), (z(B, 12), z(B, 12), None)], [(z(B, n), None, None), (z(B, n), None, None), (q0.copy(), q0.copy(), None)]],
+            "bound": [(q0.copy(), np.tile(qmin, (B, 1)), np.tile(qmax, (B, 1))), (np.full((B, n), np.pi / 2.0), None, None)],
+            "rows": [], "C": [],
+            "state": {"q0": q0, "q_ref": q0.copy(), "frames": (fl, fr), "gradient": [(1, 0, 0), (1, 1, 1)]}}
+    terms = [posture_term(abi.GRAD_MANIPULABILITY_FRAME, frame=fl, step=step, lam=lam),
+             posture_term(abi.GRAD_MANIPULABILITY_FRAME, frame=fr, step=step, lam=lam)]
+    return plan, leaf, model, terms
+
+
+def bind_posture_gradient(stack, grad, leaf, kin=None):
+    """wire make_min_effort_stack / make_coman_manipulability_stack to the device: ONE q tensor is the gradient producer's input, the
+    Postural block's actual posture, the joint limits' q and (with `kin`, a kinematics.Kinematics of the same model) the kinematics
+    producer's input; leaf["state"]["gradient"] lists (level, block, term): the producer writes term's b into that block's leaf --
+    p2, the feed-forward, of an implicit Postural block whose reference is then q itself, p0 of a Generic block.  With `kin` the wrists'
+    relative poses go into the Cartesian tasks' p0 and their Jacobians into stack.A[0]; the Cartesian references are the first
+    posture's poses.  -> (dev_leaf, grad_batch, kin_batch or None, q)"""
+    import torch
+    B, s = leaf["B"], leaf["state"]
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q = torch.as_tensor(s["q0"], **f64).contiguous()
+    out = {}
+    for (k, j, term) in s["gradient"]:
+        p0, p1, p2 = dev["task"][k][j]
+        if stack.plan.levels[k][j].kind == abi.TASK_POSTURAL:
+            dev["task"][k][j] = (q, q, p2)
+            out[term] = p2
+        else:
+            out[term] = p0
+    kb = None
+    if kin is not None:
+        frames = s["frames"]
+        poses = [dev["task"][0][i][0] for i in range(len(frames))]
+        kw = dict(frame_pose={f: poses[i] for i, f in enumerate(frames)}, frame_J={f: (stack.A[0], 6 * i) for i, f in enumerate(frames)})
+        kin.forward(q, **kw)
+        for i in range(len(frames)):
+            dev["task"][0][i] = (poses[i], poses[i].clone(), None)
+        last = len(dev["task"][1]) - 1
+        dev["task"][1][last] = (q, torch.as_tensor(s["q_ref"], **f64).contiguous(), None)
+        dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
+        kb = kin.batch_args(q, **kw)
+    return dev, grad.batch_args(q, b=out), kb, q
