@@ -233,7 +233,9 @@ __device__ __forceinline__ double colmax(double v) {
     if (NP > 32) { swap32_pair(v, a, b); v = max_raw(a, b); }
     return v;
 }
-// (inputs >= 0 or -0: non-negative floats order like unsigned integers, and v_max_u32 takes its DPP operand directly)
+// PRECONDITION: inputs >= 0 or -0 (non-negative floats order like unsigned integers, and v_max_u32 takes its DPP operand
+// directly).  The sign bit is cleared first, so -0 counts as +0 and the result is never -0; a negative input counts as its
+// magnitude and a NaN as a value above +inf -- neither is detected.
 template <int NP>
 __device__ __forceinline__ float colmax_f32(float v) {
     unsigned u = __float_as_uint(v) & 0x7fffffffu;
@@ -257,7 +259,10 @@ __device__ __forceinline__ int first_lane_equal(double v, double m) {
     return mask ? __builtin_ctzll(mask) : 64;
 }
 // two column sums for the price of one reduction network: half 0 reduces va, half 1 reduces vb, then the
-// halves exchange their totals (NP = 32; plain two reductions for NP = 64)
+// halves exchange their totals (NP = 32; plain two reductions for NP = 64).
+// PRECONDITION (NP = 32): va and vb are replicated over the halves, as every vector of the solver is.  What is computed is
+// ra = sum of va over lanes 0..31 and rb = sum of vb over lanes 32..63, both delivered to all 64 lanes: va's upper half and
+// vb's lower half are never read.
 template <int NP>
 __device__ __forceinline__ void colsum2(double va, double vb, double& ra, double& rb) {
     if (NP > 32) { ra = colsum<64>(va); rb = colsum<64>(vb); return; }
@@ -317,6 +322,11 @@ __device__ __forceinline__ int colmin_i(int v) {
 // NP = 32: BOTH HALVES MUST HOLD THE SAME CANDIDATES (they do wherever the solver reduces over 32 columns: vectors are
 // replicated over the halves).  One lane holds the minimum (the usual case): its payload is a v_readlane away; several do
 // (exact ties): the second network picks the smallest payload among them -- the same pair either way.
+// With halves that differ, the value is each half's own minimum, and the payload is the LOWER half's minimiser's for all 64
+// lanes when that is a single lane, each half's own smallest otherwise.
+// NaN candidates lose (v_min_f64 in IEEE mode, and v == m is false for them): the result is the minimum of the others and
+// its payload.  With every candidate NaN the value is NaN and the payload 0x7fffffff -- callers test the value, not the payload.
+// +0 and -0 tie.  Payloads must be below 0x7fffffff.
 template <int NP>
 __device__ __forceinline__ void colargmin(double& v, int& p) {
     const double m = colmin<NP>(v);
@@ -345,6 +355,13 @@ __device__ __forceinline__ int shift_down_i(int v) { return __shfl_down(v, 1, NP
 // ---- fp64 reciprocal / square root without the IEEE corner-case sequences -----------------------------
 // v_rcp_f64 / v_rsq_f64 seeds + Newton steps: ~1 ulp for normal arguments, far cheaper than the compiler's
 // div_scale/div_fmas/div_fixup expansion.  Arguments here are pivots/norms that are checked > 0 first.
+// PRECONDITION: the argument(s), the result and the intermediates are NORMAL numbers (for fast_div that includes 1 / b and
+// the quotient; fast_sqrt_rsqrt needs x > 0).  Outside that domain there is no IEEE corner-case handling and the Newton steps
+// turn the seed's inf / 0 into NaN: fast_rcp(+-0), fast_rcp(+-inf), fast_div(a, 0), fast_div(a, inf), fast_div(inf, b), a
+// quotient that overflows, fast_sqrt_rsqrt(0), fast_sqrt_rsqrt(inf) and fast_sqrt_rsqrt(x < 0) are all NaN (both results),
+// and fast_div(-0, b) is +0.  A caller that may hand over such an argument has to select the result away afterwards AND must
+// not let the NaN reach a reduction.  (tests/test_team_primitives.py probes all of this on the device; the measured worst
+// cases are in profiles/team_primitives_mi355x.txt.)
 __device__ __forceinline__ double fast_rcp(double x) {
     double r = __builtin_amdgcn_rcp(x);
     double e = fma(-x, r, 1.0);
@@ -353,10 +370,14 @@ __device__ __forceinline__ double fast_rcp(double x) {
     r = fma(r, e, r);
     return r;
 }
-// one Newton step only (~2 ulp): for counts and comparisons, not for values that are kept (sym_bisect_32's Sturm sequences)
+// one residual only, its correction carried to second order: r (1 + e + e^2) with e = 1 - x r leaves a relative error of e^3
+// in front of the final rounding -- three dependent fma instead of fast_rcp's four, <= 2 ulp.  (The plain Newton step
+// r + r e that stood here leaves e^2: v_rcp_f64's seed is good to about 2^-24, and the probe of tests/test_team_primitives.py
+// measured 10 ulp on an MI355X where this comment said ~2.)  For counts and comparisons, not for values that are kept.
 __device__ __forceinline__ double fast_rcp1(double x) {
     const double r = __builtin_amdgcn_rcp(x);
-    return fma(r, fma(-x, r, 1.0), r);
+    const double e = fma(-x, r, 1.0);
+    return fma(r, fma(e, e, e), r);
 }
 // binary exponent of x as frexp returns it (0 for x = 0), one instruction; x 2^e, one instruction
 __device__ __forceinline__ int frexp_exponent(double x) { return __builtin_amdgcn_frexp_exp(x); }

@@ -11,6 +11,7 @@
 #include "osot_admm.h"
 #include "osot_ehqp.h"
 #include <vector>
+#include "../probe/team_probe.h"
 
 using namespace osot;
 
@@ -237,5 +238,15 @@ extern "C" __attribute__((visibility("default"))) int emu_sym_eig32_fast(double*
 }
 extern "C" __attribute__((visibility("default"))) int emu_sym_eig32(double* K, double* E, int k) {
     emu::launch(emu_eig_kernel, 1u, 0, 64, K, E, k);
+    return 0;
+}
+
+// the probe of the wavefront primitives (tests/probe/team_probe.h) against the twin: the same text the device build compiles
+// against the product's header (tests/test_team_primitives.py); host pointers, one 64-lane block per case
+extern "C" __attribute__((visibility("default"))) int emu_team_probe(int ncase, const int* op, const int* np, const int* sarg, const double* din,
+                                                                     const int* iin, const float* fin, double* dout, int* iout, float* fout) {
+    const int rc = osot_probe::probe_check(ncase, op, np, sarg);
+    if (rc) return rc;
+    emu::launch(osot_probe::team_probe_kernel, (unsigned)ncase, 0, 64, op, np, sarg, din, iin, fin, dout, iout, fout);
     return 0;
 }

@@ -56,6 +56,24 @@ def emu_lib():
     return _emu
 
 
+_probe = None
+
+
+def team_probe_lib():
+    """the DEVICE build of the wavefront-primitive probe (tests/probe: team_probe.h against the product's osot_team.h, gfx950),
+    built on demand like emu_lib().  Its host twin is emu_lib().emu_team_probe -- same text, same arguments."""
+    global _probe
+    if _probe is None:
+        so = os.path.join(ROOT, "tests", "probe", "libosot_team_probe.so")
+        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", "osot_team.h")] + [os.path.join(ROOT, "tests", "probe", f)
+                                                                             for f in ("team_probe.h", "team_probe.hip", "build.sh")]
+        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
+            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "probe", "build.sh")])
+        import torch  # noqa: F401    (its bundled HIP runtime first, as opensot_amd.abi.lib() does: one runtime per process)
+        _probe = C.CDLL(so)
+    return _probe
+
+
 def null_batch_pointer(qb, name, level=None):
     """a batch as a caller that forgot one array hands it over: qb.name, or qb.name[level], becomes null"""
     if level is None:
