@@ -4,7 +4,6 @@ kernel source through the host lock-step emulation (tests/emu/grad_host.cpp)."""
 import ctypes as C
 import functools
 import os
-import subprocess
 
 import numpy as np
 
@@ -13,6 +12,7 @@ from opensot_amd import kinematics as kin
 from opensot_amd.gradient import grad_desc
 
 import gradient_ref as gref
+import native_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GRAVITY = (0.0, 0.0, -9.81)
@@ -106,16 +106,10 @@ _lib = None
 
 
 def grad_lib():
-    """tests/emu/libosot_grad_host.so, (re)built when a source is newer"""
+    """tests/emu/libosot_grad_host.so (tests/native_build.py)"""
     global _lib
     if _lib is None:
-        so = os.path.join(ROOT, "tests", "emu", "libosot_grad_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_grad.h", "osot_kin.h")] + \
-               [os.path.join(ROOT, "include", "osot_mi355x.h"), os.path.join(ROOT, "tests", "emu", "grad_host.cpp"),
-                os.path.join(ROOT, "tests", "emu", "osot_team.h"), os.path.join(ROOT, "tests", "emu", "hip", "hip_runtime.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
-            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build_grad.sh")])
-        L = C.CDLL(so)
+        L = native_build.load("grad_host")
         L.grad_host_gradient.argtypes = [C.POINTER(abi.KinDesc), C.POINTER(abi.GradDesc), C.POINTER(abi.GradBatch)]
         _lib = L
     return _lib

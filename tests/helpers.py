@@ -1,12 +1,13 @@
 """shared test helpers (test infrastructure)."""
 import ctypes as C
 import os
-import subprocess
 import sys
 
 import numpy as np
 
 from opensot_amd import abi, synth
+
+import native_build
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, "tests", "golden")
@@ -39,14 +40,8 @@ def emu_lib():
     """host lock-step emulation of the product kernels (tests/emu)."""
     global _emu
     if _emu is None:
-        so = os.environ.get("OSOT_EMU_LIB") or os.path.join(ROOT, "tests", "emu", "libosot_emu.so")   # (developer knob: another build of the emulator)
-        import glob
-        srcs = (glob.glob(os.path.join(ROOT, "opensot_amd", "csrc", "*.h")) + glob.glob(os.path.join(ROOT, "include", "*.h"))
-                + [f for f in glob.glob(os.path.join(ROOT, "tests", "emu", "**", "*"), recursive=True)
-                   if os.path.isfile(f) and not f.endswith(".so")])
-        if "OSOT_EMU_LIB" not in os.environ and (not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs)):
-            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build.sh")])
-        L = C.CDLL(so)
+        so = os.environ.get("OSOT_EMU_LIB")   # (developer knob: another build of the emulator, loaded as it is)
+        L = C.CDLL(so) if so else native_build.load("emu")
         L.emu_ihqp_solve.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.QpBatch), C.c_void_p, C.c_void_p]
         L.emu_stack_update.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.LeafBatch), C.POINTER(abi.AssembledOut)]
         vp = C.c_void_p
@@ -64,13 +59,8 @@ def team_probe_lib():
     built on demand like emu_lib().  Its host twin is emu_lib().emu_team_probe -- same text, same arguments."""
     global _probe
     if _probe is None:
-        so = os.path.join(ROOT, "tests", "probe", "libosot_team_probe.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", "osot_team.h")] + [os.path.join(ROOT, "tests", "probe", f)
-                                                                             for f in ("team_probe.h", "team_probe.hip", "build.sh")]
-        if not os.path.exists(so) or any(os.path.getmtime(s) > os.path.getmtime(so) for s in srcs):
-            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "probe", "build.sh")])
         import torch  # noqa: F401    (its bundled HIP runtime first, as opensot_amd.abi.lib() does: one runtime per process)
-        _probe = C.CDLL(so)
+        _probe = native_build.load("team_probe")
     return _probe
 
 
@@ -82,6 +72,28 @@ def null_batch_pointer(qb, name, level=None):
         getattr(qb, name)[level] = None
 
 
+def task_active_flags(task_active):
+    """{(level, task): bool} (Task::setActive) -> the uint8 [MAX_LEVELS * MAX_TASKS] flag array of osot_solver_set_task_active (tasks
+    not named are active); None stays None"""
+    if task_active is None:
+        return None
+    ta = np.ones(abi.MAX_LEVELS * abi.MAX_TASKS, dtype=np.uint8)
+    for (k, j), on in task_active.items():
+        ta[k * abi.MAX_TASKS + j] = 1 if on else 0
+    return ta
+
+
+def fill_level_ptrs(qb, asm, names, keep):
+    """qb.<name>[k] = the float64 array asm[name][k] of every level k, for the names asm has; the arrays handed over go to `keep`"""
+    for k in range(asm["L"]):
+        for name in names:
+            a = asm[name][k] if asm.get(name) is not None else None
+            if a is not None:
+                a = np.ascontiguousarray(a, dtype=np.float64)
+                keep.append(a)
+                getattr(qb, name)[k] = a.ctypes.data
+
+
 def emu_cascade(plan, asm, active=None, task_active=None, hot=None, drop=None):
     """run the cascade kernel body on host pointers through the emulator.  task_active: {(level, task): bool}
     (Task::setActive); asm may carry "WA" / "Wb" (levels with a non-diagonal weight, see emu_update); hot: int32
@@ -91,15 +103,7 @@ def emu_cascade(plan, asm, active=None, task_active=None, hot=None, drop=None):
     qb = abi.QpBatch()
     qb.B = B
     keep = []
-    for k in range(L):
-        for name in ("A", "b", "w", "c", "WA", "Wb"):
-            if name not in asm:
-                continue
-            a = asm[name][k]
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64)
-                keep.append(a)
-                getattr(qb, name)[k] = a.ctypes.data
+    fill_level_ptrs(qb, asm, ("A", "b", "w", "c", "WA", "Wb"), keep)
     from opensot_amd.solver import stored_rows
     for name in ("C", "lo", "up", "l", "u"):
         a = asm[name]
@@ -130,16 +134,12 @@ def emu_cascade(plan, asm, active=None, task_active=None, hot=None, drop=None):
         keep.append(act)
         qb.level_active = C.addressof(act)
     pd = plan.to_c()
-    ta = None
-    if task_active:
-        ta = (C.c_ubyte * (abi.MAX_LEVELS * abi.MAX_TASKS))(*([1] * (abi.MAX_LEVELS * abi.MAX_TASKS)))
-        for (k, j), on in task_active.items():
-            ta[k * abi.MAX_TASKS + j] = 1 if on else 0
+    ta = task_active_flags(task_active or None)
     if hot is not None:
         assert hot.dtype == np.int32 and hot.flags.c_contiguous and hot.shape == (B, L, 32 if n <= 32 else 64)
     if drop is not None:
         null_batch_pointer(qb, *drop)
-    rc = emu_lib().emu_ihqp_solve(C.byref(pd), C.byref(qb), C.cast(ta, C.c_void_p) if ta is not None else None,
+    rc = emu_lib().emu_ihqp_solve(C.byref(pd), C.byref(qb), None if ta is None else ta.ctypes.data,
                                   hot.ctypes.data if hot is not None else None)
     if drop is not None:
         return rc
@@ -445,12 +445,7 @@ def emu_nhqp(plan, asm, free_vars=None, min_sv_ratio=None, ab_regularization=Tru
     qb = abi.QpBatch()
     qb.B = B
     keep = []
-    for k in range(L):
-        for name in ("A", "b", "w"):
-            a = asm[name][k]
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64); keep.append(a)
-                getattr(qb, name)[k] = a.ctypes.data
+    fill_level_ptrs(qb, asm, ("A", "b", "w"), keep)
     for name in ("C", "lo", "up", "l", "u"):
         a = asm[name]
         if a is not None and a.size:
@@ -464,11 +459,7 @@ def emu_nhqp(plan, asm, free_vars=None, min_sv_ratio=None, ab_regularization=Tru
             if Wk is not None:
                 Wk = np.ascontiguousarray(Wk, dtype=np.float64); keep.append(Wk)
                 opt.level_W[k] = Wk.ctypes.data
-    ta = None
-    if task_active:
-        ta = np.ones(abi.MAX_LEVELS * abi.MAX_TASKS, dtype=np.uint8)
-        for (k, j), on in task_active.items():
-            ta[k * abi.MAX_TASKS + j] = 1 if on else 0
+    ta = task_active_flags(task_active or None)
     L_ = emu_lib()
     L_.emu_nhqp_solve.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.QpBatch), C.POINTER(abi.NhqpOptions), C.c_void_p]
     pd = plan.to_c()
@@ -483,17 +474,7 @@ def emu_ehqp(plan, asm, sigma_min=0.0, level_active=None, task_active=None):
     qb = abi.QpBatch()
     qb.B = B
     keep = []
-    for k in range(L):
-        for name in ("A", "b", "w"):
-            a = asm[name][k]
-            if a is not None:
-                a = np.ascontiguousarray(a, dtype=np.float64); keep.append(a)
-                getattr(qb, name)[k] = a.ctypes.data
-        for name, key in (("WA", "WA"), ("Wb", "Wb")):
-            arr = asm.get(key)
-            if arr is not None and arr[k] is not None:
-                a = np.ascontiguousarray(arr[k], dtype=np.float64); keep.append(a)
-                getattr(qb, name)[k] = a.ctypes.data
+    fill_level_ptrs(qb, asm, ("A", "b", "w", "WA", "Wb"), keep)
     dq = np.zeros((B, n)); st = np.full(B, -1, dtype=np.int32); xl = np.zeros((B, L, n))
     qb.dq, qb.status, qb.x_levels = dq.ctypes.data, st.ctypes.data, xl.ctypes.data
     if level_active is not None:
@@ -501,12 +482,7 @@ def emu_ehqp(plan, asm, sigma_min=0.0, level_active=None, task_active=None):
         qb.level_active = la.ctypes.data
     L_ = emu_lib()
     L_.emu_ehqp_solve.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.QpBatch), C.c_double, C.c_void_p]
-    ta = None
-    if task_active is not None:      # {(level, task): False} -> the [MAX_LEVELS * MAX_TASKS] flag array of osot_solver_set_task_active
-        ta = np.ones(abi.MAX_LEVELS * abi.MAX_TASKS, dtype=np.uint8)
-        for (k, j), on in task_active.items():
-            ta[k * abi.MAX_TASKS + j] = 1 if on else 0
-        keep.append(ta)
+    ta = task_active_flags(task_active)
     pd = plan.to_c()
     rc = L_.emu_ehqp_solve(C.byref(pd), C.byref(qb), float(sigma_min), None if ta is None else ta.ctypes.data)
     assert rc == 0
@@ -591,19 +567,10 @@ def max_where(mask, values):
     return float(values[mask].max()) if np.any(mask) else 0.0
 
 
-_big = None
-
-
 def big_host_solve(H, g, A, lA, uA, l, u, eps_abs, max_iter=0):
     """one QP through the WIDE solver (opensot_amd/csrc/osot_qp_big.h: 65 .. 128 variables) compiled for the host with a team of one
     thread (tests/emu/big_host.cpp).  Returns (status, x, iterations)."""
-    global _big
-    if _big is None:
-        so = os.path.join(ROOT, "tests", "emu", "libosot_big_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_qp_big.h", "osot_qp_tol.h")] + [os.path.join(ROOT, "tests", "emu", "big_host.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
-            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build.sh")])
-        _big = C.CDLL(so)
+    _big = native_build.load("big_host")
     dp = C.POINTER(C.c_double)
     n = H.shape[0]
     nc = 0 if A is None else A.shape[0]

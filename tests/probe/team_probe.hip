@@ -1,5 +1,5 @@
 // tests/probe/team_probe.hip -- TEST INFRASTRUCTURE ONLY: the device build of tests/probe/team_probe.h against the product's
-// opensot_amd/csrc/osot_team.h (tests/probe/build.sh -> libosot_team_probe.so; loaded by tests/helpers.py:team_probe_lib).
+// opensot_amd/csrc/osot_team.h (tests/native_build.py team_probe -> libosot_team_probe.so; loaded by tests/helpers.py:team_probe_lib).
 #include "team_probe.h"
 
 #define PROBE_HIP(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { rc = (int)e_; goto done; } } while (0)

@@ -4,15 +4,14 @@ contact and one instance at a time, in the order the reference builds its matric
 so every comparison with it goes through the GENERIC TWIN of a plan: the same stack with each surface block replaced by an
 OSOT_ROWS_GENERIC block carrying the rows written out here."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
 from opensot_amd import abi
 from opensot_amd.plan import Rows, StackPlan
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+import native_build
+
 SURFACE_KINDS = {abi.ROWS_WRENCH_FRICTION_CONE: 5, abi.ROWS_COP: 4, abi.ROWS_NORMAL_TORQUE: 8}
 
 
@@ -105,12 +104,7 @@ _lib = None
 def surface_lib():
     global _lib
     if _lib is None:
-        so = os.path.join(ROOT, "tests", "emu", "libosot_surface_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_kernels.h", "osot_id.h", "osot_host_plan.h")] + \
-               [os.path.join(ROOT, "include", "osot_mi355x.h"), os.path.join(ROOT, "tests", "emu", "surface_host.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
-            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build_surface.sh")])
-        L = C.CDLL(so)
+        L = native_build.load("surface_host")
         vp = C.c_void_p
         L.surf_stack_update.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.LeafBatch), C.POINTER(abi.AssembledOut), C.c_int]
         L.surf_id_rows.argtypes = [C.POINTER(abi.IdModel), vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, vp, vp, vp]

@@ -8,7 +8,6 @@ worst 1.6e-15 (com_Jdot_qdot on humanoid32; M 5.0e-16, h 3.6e-16, frame Jdot qdo
 import ctypes as C
 import json
 import os
-import subprocess
 
 import numpy as np
 import pytest
@@ -17,6 +16,7 @@ from opensot_amd import abi
 from opensot_amd import kinematics as kin
 
 import dyn_ref
+import native_build
 from helpers import emu_kinematics
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,16 +29,10 @@ _lib = None
 
 
 def dyn_lib():
-    """tests/emu/libosot_dyn_host.so, (re)built when a source is newer"""
+    """tests/emu/libosot_dyn_host.so (tests/native_build.py)"""
     global _lib
     if _lib is None:
-        so = os.path.join(ROOT, "tests", "emu", "libosot_dyn_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_dyn.h", "osot_kin.h")] + \
-               [os.path.join(ROOT, "include", "osot_mi355x.h"), os.path.join(ROOT, "tests", "emu", "dyn_host.cpp"),
-                os.path.join(ROOT, "tests", "emu", "osot_team.h")]
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
-            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build_dyn.sh")])
-        L = C.CDLL(so)
+        L = native_build.load("dyn_host")
         L.dyn_host_dynamics.argtypes = [C.POINTER(abi.KinDesc), C.POINTER(abi.DynDesc), C.POINTER(abi.DynBatch)]
         _lib = L
     return _lib

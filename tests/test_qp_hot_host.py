@@ -1,5 +1,5 @@
 """Hot start of the wide explicit QP (65 .. 128 variables, opensot_amd/csrc/osot_qp_big.h, big::solve<true>) on the host: the SAME
-source the product runs as a 256-thread workgroup, compiled by tests/emu/build_big_hot.sh with a team of one thread and with the
+source the product runs as a 256-thread workgroup, compiled by tests/native_build.py (big_hot_host) with a team of one thread and with the
 turn-taking team of tests/emu/cascade_wide_host.cpp.  No GPU.
 
 Problems: random_qp(default_rng(31), 6, n, nc, n_eq, box=True) with g *= 4, eps 1e-9, at (n, nc, n_eq) = (65, 10, 0), (72, 24, 4),
@@ -13,9 +13,9 @@ import subprocess
 import numpy as np
 import pytest
 
+import native_build
 from helpers import ROOT, big_host_solve, kkt_check, random_qp
 
-EMU = os.path.join(ROOT, "tests", "emu")
 EPS = 1e-9
 HOT_LEN = 128
 SHAPES = [(65, 10, 0), (72, 24, 4), (128, 40, 0)]
@@ -24,13 +24,8 @@ _lib = None
 
 
 def _build(what):
-    """the library the tests load ("lib") or the stand-alone sanitizer program ("asan"), rebuilt when a source is newer"""
-    out = os.path.join(EMU, "libosot_big_hot_host.so" if what == "lib" else "big_hot_asan")
-    srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_qp_big.h", "osot_qp_tol.h")] + \
-           [os.path.join(EMU, "big_hot_host.cpp"), os.path.join(EMU, "build_big_hot.sh")]
-    if not os.path.exists(out) or any(os.path.getmtime(f) > os.path.getmtime(out) for f in srcs):
-        subprocess.check_call(["sh", os.path.join(EMU, "build_big_hot.sh"), what])
-    return out
+    """the library the tests load ("lib") or the stand-alone sanitizer program ("asan"), rebuilt when stale"""
+    return native_build.ensure("big_hot_host" if what == "lib" else "big_hot_asan")
 
 
 def hot_lib():

@@ -3,13 +3,13 @@ cascade source (opensot_amd/csrc/osot_cascade_wide.h) compiled for the host (tes
 thread against the oracle, and with a turn-taking team of four threads against the team of one under two schedules."""
 import ctypes as C
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 from opensot_amd import abi, synth
 from opensot_amd.solver import stored_rows
+import native_build
 from helpers import null_batch_pointer
 from oracle import pyoracle
 
@@ -20,12 +20,7 @@ _wide = None
 def wide_lib():
     global _wide
     if _wide is None:
-        so = os.path.join(ROOT, "tests", "emu", "libosot_wide_host.so")
-        srcs = [os.path.join(ROOT, "opensot_amd", "csrc", f) for f in ("osot_cascade_wide.h", "osot_qp_big.h", "osot_qp_tol.h", "osot_plan_shape.h")] + \
-               [os.path.join(ROOT, "tests", "emu", "cascade_wide_host.cpp")]
-        if not os.path.exists(so) or any(os.path.getmtime(f) > os.path.getmtime(so) for f in srcs):
-            subprocess.check_call(["sh", os.path.join(ROOT, "tests", "emu", "build_wide.sh")])
-        _wide = C.CDLL(so)
+        _wide = native_build.load("wide_host")
         _wide.wide_host_ihqp.argtypes = [C.POINTER(abi.PlanDesc), C.POINTER(abi.QpBatch), C.c_void_p, C.c_int, C.c_int]
         _wide.wide_host_tolerances.argtypes = [C.POINTER(C.c_double)]
         _wide.wide_host_tolerances.restype = None
