@@ -395,12 +395,32 @@ int osot_solver_create(const osot_plan_desc* plan, int max_batch, int device, os
  *                                     bit-identical to the two calls;
  *   osot_solver_set_schedule, osot_solver_set_specialisation ... accepted, without effect (instances are dispatched in order);
  *   osot_solver_resident_waves ...... the instances in flight: resident workgroups of the wide kernel (one instance each);
+ *                                     the cold kernel's figure -- a hot launch (below) never runs more workgroups than that;
+ *   osot_ihqp_solve_hot, osot_cycle_hot ... the same two calls with every level's working set carried from cycle to cycle in a
+ *                                     device array the CALLER owns (below); osot_solver_set_hotstart stays refused here;
  *   osot_nhqp_solve, osot_ehqp_solve, osot_control_cycle, osot_control_rollout, osot_solver_set_hotstart(s, 1),
  *   osot_solver_profile_phases, osot_solver_resident_waves_nhqp ... OSOT_ERR_UNSUPPORTED with a reason.
  * A level's status and accepted_slack follow the wavefront route's rules (round-off of the levels above: at most
  * min(1e-6 * max(1, |bound|), 1e-5), status SOLVED). */
 int osot_solver_create_wide(const osot_plan_desc* plan, int max_batch, int device, osot_solver** out);
 int osot_solver_destroy(osot_solver* s);
+
+/* Hot start on the WORKGROUP route (reference: QPOasesBackEnd.cpp:258-285, SQProblem.cpp:149-193), with caller-owned state as in
+ * osot_qp_solve_batch_hot.  hot_state: device int32 [B][n_levels][128] (osot_solver_hot_state_ints: n_levels * 128 per instance), row i
+ * = instance i of the batch; an entry is 2 * position + (upper side ? 1 : 0) of a position in that LEVEL's row table -- position
+ * < n: the box, n + r: constraint row r (global and task-local rows) -- or -1 for none.  Fill it with -1 before the first call (and
+ * an instance's row whenever that robot is reset); several states (one per pipelined sub-batch) may be used with one solver.
+ * Per instance, every ACTIVE level reads its list before its solve (re-adding the constraints as in osot_solver_set_hotstart) and
+ * rewrites it, compacted, with the inequality working set it ended with; a level that fails records 128 x -1 and ends the instance,
+ * the lists of the levels below it, and of levels switched off by level_active, are left as they are.  Entries that are no
+ * inequality of the level (out of range, equality or optimality rows, infinite sides, rows of an inactive task) are skipped: any
+ * content is safe.  The answer does not depend on the lists beyond round-off, only the iteration counts do.
+ * hot_state == NULL: exactly osot_ihqp_solve / osot_cycle.  No allocation and no synchronisation: capturable into a HIP graph like
+ * osot_cycle on a wide handle.  A handle of osot_solver_create: OSOT_ERR_UNSUPPORTED (use osot_solver_set_hotstart there). */
+int osot_solver_hot_state_ints(osot_solver* s, int* ints_per_instance);
+int osot_ihqp_solve_hot(osot_solver* s, const osot_qp_batch* batch, int* hot_state, void* hip_stream);
+int osot_cycle_hot(osot_solver* s, const osot_leaf_batch* leaf, const osot_assembled_out* out, const osot_qp_batch* batch,
+                   int* hot_state, void* hip_stream);
 
 /* AutoStack::update() for B instances: leaf inputs -> b_k, w_k, merged box, constraint rows.
  * Stream-ordered on `hip_stream` (a hipStream_t passed as void*, NULL = default stream). */
@@ -437,7 +457,8 @@ int osot_solver_set_schedule(osot_solver* s, int mode);
  * per instance index, so instance i of consecutive batches should be the same robot.  Calling it (again) with
  * enabled != 0 forgets the recorded sets; 0 (default) = every solve is a cold start and nothing is recorded.  The answer
  * does not depend on the mode beyond round-off (each level's minimiser is unique); the iteration counts do: it pays
- * when the active sets persist from cycle to cycle and costs two iterations per constraint that has left the set. */
+ * when the active sets persist from cycle to cycle and costs two iterations per constraint that has left the set.
+ * The wavefront route only: a wide handle refuses enabled != 0 and hot-starts through osot_ihqp_solve_hot / osot_cycle_hot. */
 int osot_solver_set_hotstart(osot_solver* s, int enabled);
 /* Kernel instantiation by plan structure.  enabled != 0 (default): a plan WITHOUT constraint rows (the bounds l <= x <= u are
  * its only inequalities: a velocity stack with joint / velocity limits, BASELINE configs 2 and 3) of at most 32 variables runs

@@ -197,6 +197,7 @@ SYMBOLS = [
     "osot_backend_get_num_variables", "osot_backend_get_num_constraints",
     "osot_qp_solve_batch", "osot_qp_solve_batch_admm", "osot_qp_solve_batch_admm_warm",
     "osot_qp_hot_state_ints", "osot_qp_solve_batch_hot",
+    "osot_solver_hot_state_ints", "osot_ihqp_solve_hot", "osot_cycle_hot",
     "osot_comm_unique_id", "osot_comm_create", "osot_comm_destroy", "osot_allgather_dq", "osot_abi_layout",
 ]
 
@@ -251,6 +252,9 @@ def lib():
     L.osot_solver_set_timing.argtypes = [vp, C.c_int]
     L.osot_solver_set_schedule.argtypes = [vp, C.c_int]
     L.osot_solver_set_hotstart.argtypes = [vp, C.c_int]
+    L.osot_solver_hot_state_ints.argtypes = [vp, ip]
+    L.osot_ihqp_solve_hot.argtypes = [vp, C.POINTER(QpBatch), vp, vp]
+    L.osot_cycle_hot.argtypes = [vp, C.POINTER(LeafBatch), C.POINTER(AssembledOut), C.POINTER(QpBatch), vp, vp]
     L.osot_solver_set_specialisation.argtypes = [vp, C.c_int]
     L.osot_solver_set_task_active.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.osot_solver_resident_waves.argtypes = [vp, ip]

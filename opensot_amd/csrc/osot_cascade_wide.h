@@ -98,8 +98,13 @@ struct TableRows {
 OSOT_BIG_FN unsigned long long unit_code(int col) { return ((unsigned long long)col << 1) | 1ull; }
 
 // one instance by the whole team; smem = shared_bytes(P.n, P.nrows), slot = 2 n^2 doubles
-template <class Team>
-OSOT_BIG_FN void cascade_instance(const Team& tm, const Plan& P, const Batch& D, const long long inst, char* smem, double* slot) {
+// HOT: every active level's solve is big::solve<true> on its own list of the caller's state, hot [B][P.L][big::kHotLen] (osot_ihqp_solve_hot):
+// row inst belongs to instance inst of the batch, whichever workgroup solves it.  Level k's list holds positions in level k's row table
+// (box, global rows, this level's task-local rows), read before the level's solve and rewritten after it -- all -1 where the level
+// fails; the list of a level that is switched off, or that a failure above keeps from running, is not touched.  The cold
+// instantiation carries none of it.
+template <bool HOT = false, class Team>
+OSOT_BIG_FN void cascade_instance(const Team& tm, const Plan& P, const Batch& D, const long long inst, char* smem, double* slot, int* hot = nullptr) {
     const int n = P.n, R = P.nrows;
     const bool t0 = tm.tid == 0;
     const big::Shared sh = big::carve(smem, n, R);
@@ -241,7 +246,16 @@ OSOT_BIG_FN void cascade_instance(const Team& tm, const Plan& P, const Batch& D,
         a.x = xk; a.status = lst; a.iters = lst + 1;
         a.Lw = Lw; a.J = Jw;
         a.accept_slack = true; a.slack = slack;
-        big::solve(tm, a, sh, rows);
+        if constexpr (HOT) {
+            // (a null state: the level starts cold and records nothing.  The launch layer hands a null state to the cold kernel, so
+            // the test is never false on the device; with it the kernel allocates 124 VGPRs, without it 130 -- one workgroup per CU
+            // less: profiles/wide_hot_codegen.txt)
+            if (hot) a.hot_in = a.hot_out = hot + ((size_t)inst * P.L + k) * big::kHotLen;
+            big::solve<true>(tm, a, sh, rows);
+        } else {
+            (void)hot;
+            big::solve(tm, a, sh, rows);
+        }
         const int st = lst[0];
         iters_total += lst[1];
         tm.sync();                                           // (everybody has read the level's status before the next one)
@@ -284,6 +298,16 @@ __global__ void __launch_bounds__(256) osot_cascade_wide_kernel(const wide::Plan
     double* slot = D.work + (size_t)blockIdx.x * 2 * (size_t)P.n * P.n;
     for (long long inst = blockIdx.x; inst < D.B; inst += gridDim.x) {
         wide::cascade_instance(tm, P, D, inst, osot_wide_smem, slot);
+    }
+}
+// the same walk with every level's working set carried from call to call (osot_ihqp_solve_hot / osot_cycle_hot): same LDS, same
+// workspace slot; the state is indexed by the INSTANCE, never by the workgroup
+__global__ void __launch_bounds__(256) osot_cascade_wide_hot_kernel(const wide::Plan P, const wide::Batch D, int* const hot) {
+    extern __shared__ __attribute__((aligned(16))) char osot_wide_smem[];
+    const BigTeamDev tm{(int)threadIdx.x, (int)blockDim.x};
+    double* slot = D.work + (size_t)blockIdx.x * 2 * (size_t)P.n * P.n;
+    for (long long inst = blockIdx.x; inst < D.B; inst += gridDim.x) {
+        wide::cascade_instance<true>(tm, P, D, inst, osot_wide_smem, slot, hot);
     }
 }
 #endif

@@ -149,6 +149,7 @@ struct osot_solver {
     int wide = 0;
     double* d_work = nullptr;   // [wide_grid][2][n][n]: L and J of every resident workgroup, allocated once
     int wide_grid = 0;          // workgroups of a launch: the resident ones, at most max_batch
+    int wide_grid_hot = 0;      // the same for osot_cascade_wide_hot_kernel (by its own occupancy; never more than wide_grid: the workspace)
     size_t wide_lds = 0;
 };
 
@@ -348,11 +349,18 @@ int osot_solver_create_wide(const osot_plan_desc* plan, int max_batch, int devic
     HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, osot_cascade_wide_kernel, 256, lds));
     HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
     if (per_cu < 1 || cus < 1) return fail(OSOT_ERR_UNSUPPORTED, "the wide cascade kernel does not fit a CU for this plan");
+    // the hot kernel (osot_ihqp_solve_hot / osot_cycle_hot): same LDS, its own occupancy
+    rc = ensure_lds(osot_cascade_wide_hot_kernel, lds);
+    if (rc != OSOT_OK) return rc;
+    int per_cu_hot = 0;
+    HIP_TRY(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_hot, osot_cascade_wide_hot_kernel, 256, lds));
+    if (per_cu_hot < 1) return fail(OSOT_ERR_UNSUPPORTED, "the wide cascade kernel does not fit a CU for this plan");
     osot_solver* s = solver_new(*plan, max_batch, device);
     s->wide = 1;
     s->wide_lds = lds;
     s->slots = per_cu * cus;
     s->wide_grid = max_batch < s->slots ? max_batch : s->slots;
+    s->wide_grid_hot = per_cu_hot * cus < s->wide_grid ? per_cu_hot * cus : s->wide_grid;
     return solver_finish(s, hipMalloc(&s->d_work, sizeof(double) * 2 * (size_t)P.n * P.n * (size_t)s->wide_grid) == hipSuccess, out);
 }
 
@@ -582,15 +590,17 @@ int osot_solver_kernel_time_ms(osot_solver* s, int reset, double* avg_ms, int* l
     return OSOT_OK;
 }
 
+// wide_hot: the caller's hot-start state of osot_ihqp_solve_hot / osot_cycle_hot (wide handles only)
 static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused = nullptr,
-                       const DevControl* control = nullptr);
+                       const DevControl* control = nullptr, int* wide_hot = nullptr);
 
 int osot_ihqp_solve(osot_solver* s, const osot_qp_batch* b, void* hip_stream) {
     return ihqp_launch(s, b, hip_stream, nullptr);
 }
 
-int osot_cycle(osot_solver* s, const osot_leaf_batch* leaf, const osot_assembled_out* out, const osot_qp_batch* b,
-               void* hip_stream) {
+// osot_cycle and osot_cycle_hot: the update's arguments, then the launch (hot_state: wide handles only, null = cold)
+static int cycle_impl(osot_solver* s, const osot_leaf_batch* leaf, const osot_assembled_out* out, const osot_qp_batch* b,
+                      int* hot_state, void* hip_stream) {
     if (!s || !leaf || !out || !b) return fail(OSOT_ERR_INVALID, "null argument");
     if (leaf->B != b->B) return fail(OSOT_ERR_INVALID, "leaf and batch disagree on B");
     if (leaf->B < 0 || leaf->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
@@ -601,7 +611,36 @@ int osot_cycle(osot_solver* s, const osot_leaf_batch* leaf, const osot_assembled
     if (rc != OSOT_OK) return fail(rc, why);
     // developer knob: OSOT_DEBUG_CYCLE_PROF=<device pointer, hex> receives [B][2] int64 cycle counts (update, cascade)
     static const char* dbg = getenv("OSOT_DEBUG_CYCLE_PROF");
-    return ihqp_launch(s, b, hip_stream, dbg ? (long long*)strtoull(dbg, nullptr, 16) : nullptr, &U);
+    return ihqp_launch(s, b, hip_stream, dbg ? (long long*)strtoull(dbg, nullptr, 16) : nullptr, &U, nullptr, hot_state);
+}
+
+int osot_cycle(osot_solver* s, const osot_leaf_batch* leaf, const osot_assembled_out* out, const osot_qp_batch* b,
+               void* hip_stream) {
+    return cycle_impl(s, leaf, out, b, nullptr, hip_stream);
+}
+
+// the hot calls are the wide route's: the wavefront route keeps its state in the solver
+static int refuse_wavefront_hot(const osot_solver* s, const char* what) {
+    if (s && !s->wide) return fail(OSOT_ERR_UNSUPPORTED, std::string(what) + " takes a handle of osot_solver_create_wide; the wavefront route hot-starts through osot_solver_set_hotstart");
+    return OSOT_OK;
+}
+
+int osot_solver_hot_state_ints(osot_solver* s, int* ints_per_instance) {
+    if (!s || !ints_per_instance) return fail(OSOT_ERR_INVALID, "null argument");
+    if (const int r = refuse_wavefront_hot(s, "osot_solver_hot_state_ints")) return r;
+    *ints_per_instance = s->plan.n_levels * big::kHotLen;
+    return OSOT_OK;
+}
+
+int osot_ihqp_solve_hot(osot_solver* s, const osot_qp_batch* b, int* hot_state, void* hip_stream) {
+    if (const int r = refuse_wavefront_hot(s, "osot_ihqp_solve_hot")) return r;
+    return ihqp_launch(s, b, hip_stream, nullptr, nullptr, nullptr, hot_state);
+}
+
+int osot_cycle_hot(osot_solver* s, const osot_leaf_batch* leaf, const osot_assembled_out* out, const osot_qp_batch* b,
+                   int* hot_state, void* hip_stream) {
+    if (const int r = refuse_wavefront_hot(s, "osot_cycle_hot")) return r;
+    return cycle_impl(s, leaf, out, b, hot_state, hip_stream);
 }
 
 int osot_solver_profile_phases(osot_solver* s, const osot_qp_batch* b, long long* cycles, void* hip_stream) {
@@ -630,7 +669,8 @@ static int timed_end(osot_solver* s, hipStream_t st, const TimedLaunch& t) {
 }
 
 // the workgroup route: osot_ihqp_solve, and osot_cycle as TWO launches on the stream (osot_update_kernel, then the cascade)
-static int wide_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control) {
+// hot: [B][n_levels][big::kHotLen] device ints of the caller (osot_ihqp_solve_hot) -> the hot kernel; null -> the cold one
+static int wide_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control, int* hot) {
     if (prof) return refuse_wide(s, "phase profiling");
     if (control) return refuse_wide(s, "the fused control cycle / rollout");
     const osot_plan_desc& pl = s->plan;
@@ -649,8 +689,10 @@ static int wide_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
     }
     TimedLaunch tl;
     if (int r = timed_begin(s, st, tl)) return r;
-    const unsigned grid = (unsigned)(b->B < s->wide_grid ? b->B : s->wide_grid);
-    hipLaunchKernelGGL(osot_cascade_wide_kernel, dim3(grid), dim3(256), s->wide_lds, st, P, D);
+    const int cap = hot ? s->wide_grid_hot : s->wide_grid;
+    const unsigned grid = (unsigned)(b->B < cap ? b->B : cap);
+    if (hot) hipLaunchKernelGGL(osot_cascade_wide_hot_kernel, dim3(grid), dim3(256), s->wide_lds, st, P, D, hot);
+    else hipLaunchKernelGGL(osot_cascade_wide_kernel, dim3(grid), dim3(256), s->wide_lds, st, P, D);
     HIP_TRY(hipGetLastError());
     if (int r = timed_end(s, st, tl)) return r;
     return OSOT_OK;
@@ -664,13 +706,13 @@ struct IhqpLaunch {
     int operator()(void (*k)(DevUpdate, DevPlan, DevBatch, DevControl)) const { hipLaunchKernelGGL(k, dim3(grid), dim3(64), lds, st, *fused, P, D, *control); return OSOT_OK; }
 };
 
-static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control) {
+static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream, long long* prof, const DevUpdate* fused, const DevControl* control, int* wide_hot) {
     if (!s || !b) return fail(OSOT_ERR_INVALID, "null solver/batch");
     if (b->B < 0 || b->B > s->max_batch) return fail(OSOT_ERR_INVALID, "batch size exceeds max_batch");
     if (b->B == 0) return OSOT_OK;   // empty batch: nothing to do
     DeviceGuard guard(s->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
-    if (s->wide) return wide_launch(s, b, hip_stream, prof, fused, control);
+    if (s->wide) return wide_launch(s, b, hip_stream, prof, fused, control, wide_hot);
     const osot_plan_desc& pl = s->plan;
     DevPlan P; int T; size_t lds;
     make_dev_plan(pl, b->level_active, P, T, lds, s->any_inactive ? s->task_active : nullptr);

@@ -41,7 +41,8 @@ class BatchedStack:
 
     def __init__(self, plan: StackPlan, max_batch: int, device: int = 0, want_levels: bool = True, route: str = "auto"):
         """route: "wavefront" (osot_solver_create, n <= 64: one wavefront per instance), "wide" (osot_solver_create_wide, n <= 128:
-        one 256-thread workgroup per instance; nHQP / eHQP, the fused control cycle, hot start and phase profiling are refused there),
+        one 256-thread workgroup per instance; nHQP / eHQP, the fused control cycle, set_hotstart and phase profiling are refused
+        there: the wide route hot-starts from a state the caller owns, hot_state() and solve / cycle(hot=...)),
         "auto" (default): the wavefront route up to 64 variables, the wide route beyond."""
         if route not in ("auto", "wavefront", "wide"):
             raise ValueError(f"unknown route {route!r}")
@@ -175,9 +176,9 @@ class BatchedStack:
                   "osot_stack_update")
         return lb.B
 
-    def cycle(self, dev_leaf, write_weights=True, cached=False):
+    def cycle(self, dev_leaf, write_weights=True, cached=False, hot=None):
         """one control cycle, `stack->update(); solver->solve(dq)` (coman_ik.cpp:186-192), in ONE launch: same results as
-        update() followed by solve()"""
+        update() followed by solve().  hot: a tensor of hot_state() (the wide route: osot_cycle_hot)"""
         # the three argument structs only hold pointers and sizes: they are rebuilt when a tensor they point at has been
         # replaced (the per-cycle Jacobian sets, the gather's send block ...), not on every call -- building them is ~30 us
         # of host time, a fifth of the launch they describe
@@ -197,6 +198,10 @@ class BatchedStack:
                     self._cycle_args.clear()
                 self._cycle_args[key] = hit
         lb, out, qb, _ = hit
+        if hot is not None:
+            abi.check(self._lib.osot_cycle_hot(self._h, C.byref(lb), C.byref(out), C.byref(qb), self._hot_ptr(hot, lb.B),
+                                               _stream_ptr(self.device, self.stream)), "osot_cycle_hot")
+            return lb.B
         abi.check(self._lib.osot_cycle(self._h, C.byref(lb), C.byref(out), C.byref(qb), _stream_ptr(self.device, self.stream)), "osot_cycle")
         return lb.B
 
@@ -259,10 +264,33 @@ class BatchedStack:
             qb.level_active = C.cast(self._act, C.c_void_p)
         return qb
 
-    def solve(self, B):
-        """stream-ordered; results in self.dq[:B], self.status[:B] (device)."""
+    def solve(self, B, hot=None):
+        """stream-ordered; results in self.dq[:B], self.status[:B] (device).  hot: a tensor of hot_state() (the wide route:
+        osot_ihqp_solve_hot) -- every level starts from the working set it ended with in the previous call with that tensor"""
         qb = self._qp_batch(B)
+        if hot is not None:
+            abi.check(self._lib.osot_ihqp_solve_hot(self._h, C.byref(qb), self._hot_ptr(hot, B), _stream_ptr(self.device, self.stream)),
+                      "osot_ihqp_solve_hot")
+            return
         abi.check(self._lib.osot_ihqp_solve(self._h, C.byref(qb), _stream_ptr(self.device, self.stream)), "osot_ihqp_solve")
+
+    def hot_state(self, B=None):
+        """the caller-owned hot-start state of the wide route for B (default max_batch) instances: int32 (B, L * 128) on the device,
+        every entry -1 (no working set recorded: the first solve is a cold start); row i belongs to instance i.  Writing -1 to a
+        row resets that robot.  On the wavefront route this raises with the ABI's reason (set_hotstart is the switch there)."""
+        v = C.c_int(0)
+        abi.check(self._lib.osot_solver_hot_state_ints(self._h, C.byref(v)), "osot_solver_hot_state_ints")
+        return torch.full((self.max_batch if B is None else int(B), v.value), -1, dtype=torch.int32, device=self.device)
+
+    def _hot_ptr(self, hot, B):
+        """the device pointer of a hot state for B instances; its shape is checked here, not trusted (the kernel indexes it as
+        (inst * L + level) * 128 + entry)"""
+        if self.route == "wide":
+            cols = self.plan.L * 128
+            if not (isinstance(hot, torch.Tensor) and hot.is_cuda and hot.device == self.device and hot.dtype == torch.int32
+                    and hot.is_contiguous() and hot.dim() == 2 and hot.shape[0] >= B and hot.shape[1] == cols):
+                raise ValueError(f"hot must be a contiguous int32 tensor [>= {B}][{cols}] on {self.device} (BatchedStack.hot_state)")
+        return _dev_ptr(hot)
 
     def solve_nhqp(self, B, free_vars=None, min_sv_ratio=None, ab_regularization=True, selective_ns_regularization=True, level_W=None):
         """Solver::solve() with the reference's NULL-SPACE front-end, OpenSoT::solvers::nHQP (nHQP.cpp:155-204), on the same
