@@ -817,7 +817,18 @@ int osot_computed_torque(const osot_id_model* m, const double* x, double* tau, i
  *   the tree's generalised coordinates, so with the usual floating-base chain their first six rows are the floating base's;
  *   frame_Jdot_qdot = [classical acceleration of the frame origin; angular acceleration] at qddot = 0, world frame, such that
  *   d/dt (J qdot) = J qddot + Jdot qdot with the world-frame J osot_kinematics writes; com_Jdot_qdot likewise for the CoM.
- * M is written from one computed value per unordered pair (exactly symmetric). */
+ * M is written from one computed value per unordered pair (exactly symmetric).
+ * Centroidal momentum (what tasks::velocity::AngularMomentum / LinearMomentum, tasks::acceleration::AngularMomentum and
+ * tasks::force::CoM ask computeCentroidalMomentumMatrix / computeCentroidalMomentum for):
+ *   the 6 x n matrix is [linear (3 rows); angular (3 rows)] -- the reference reads block(0,0,3,n) as linear and block(3,0,3,n)
+ *   as angular -- in the WORLD axes about the instance's CENTRE OF MASS; its columns are the tree's generalised coordinates
+ *   (the floating base of this project is three prismatic and three revolute virtual joints); momentum = matrix * qdot.
+ *   cmm_lin and cmm_ang are two pointers so that the three rows of an AngularMomentum task land in a level's A_k next to
+ *   other blocks: exactly n doubles per row are written, columns n .. ld-1 and the gaps between rows and instances are left
+ *   alone, so with ld = the plan's n the rows [A_ang 0] of an inverse-dynamics level go into a zero-initialised A_k.
+ *   ang_mom_b is the b of acceleration::AngularMomentum (AngularMomentum.cpp:31-60) with CMMdot * v = 0 as in the reference.
+ *   The reference's tasks zero their references after every update; here the caller owns and rewrites the reference arrays.
+ *   Like every model quantity here, parity with xbot2 is unpinned (xbot2_interface is not vendored). */
 typedef struct {
     double inertia[OSOT_KIN_MAX_JOINTS][6];  /* Ixx Ixy Ixz Iyy Iyz Izz of the link joint j moves, about ITS CENTRE OF MASS
                                                 (osot_kin_desc.com[j]), axes of the joint frame; all zero = point mass       */
@@ -835,6 +846,21 @@ typedef struct {
                                                               land in a task's leaf array p1                                */
     double* com_Jdot_qdot;                   /* 3 doubles per instance, or NULL                                             */
     long long com_Jdot_qdot_stride;          /* (3 when dense)                                                              */
+    /* -- centroidal momentum (computeCentroidalMomentumMatrix / computeCentroidalMomentum); zero / NULL everywhere = none -- */
+    double* cmm_lin;                         /* first of the 3 LINEAR rows of the momentum matrix in instance 0, or NULL     */
+    long long cmm_lin_stride;                /* doubles from one instance to the next (>= 3 * ld)                            */
+    int cmm_lin_ld;                          /* row length in doubles, 0 = n; exactly n doubles of each row are written      */
+    double* cmm_ang;                         /* the 3 ANGULAR rows, likewise: e.g. a Generic block's rows in a level's A_k   */
+    long long cmm_ang_stride;
+    int cmm_ang_ld;
+    double* momentum;                        /* [linear (3); angular (3)] per instance, or NULL; zeros when qdot is NULL     */
+    long long momentum_stride;               /* (6 when dense)                                                              */
+    double* ang_mom_b;                       /* 3 doubles per instance, or NULL: Ldot_d + lambda K (L_d - L_angular)         */
+    long long ang_mom_b_stride;              /* (3 when dense): lets it land in a task's leaf array p0                       */
+    const double* ang_mom_ref;               /* L_d [B][3]; NULL = L_d is the actual momentum (b = Ldot_d)                   */
+    const double* ang_mom_rate_ref;          /* Ldot_d [B][3]; NULL = zero                                                   */
+    double ang_mom_gain[9];                  /* K, row-major; all nine zero = the identity                                   */
+    double ang_mom_lambda;
 } osot_dyn_batch;
 typedef struct osot_dyn osot_dyn;
 /* tree: what osot_kin_create takes (frames included; collision pairs are ignored).  Refused with OSOT_ERR_INVALID before any
@@ -843,7 +869,9 @@ typedef struct osot_dyn osot_dyn;
 int osot_dyn_create(const osot_kin_desc* tree, const osot_dyn_desc* inertia, int device, osot_dyn** out);
 int osot_dyn_destroy(osot_dyn* d);
 /* Stream-ordered, no allocation, capturable.  Jdot qdot of a frame with frame_base != 0 or frame_body != 0 is refused
- * (OSOT_ERR_UNSUPPORTED; the reference leaves the relative case open as well, acceleration/Cartesian.cpp:144). */
+ * (OSOT_ERR_UNSUPPORTED; the reference leaves the relative case open as well, acceleration/Cartesian.cpp:144).  Refused with
+ * OSOT_ERR_INVALID before any device is touched: a cmm row length below n, a cmm stride below 3 * ld, momentum_stride < 6,
+ * ang_mom_b_stride < 3, ang_mom_ref / ang_mom_rate_ref without ang_mom_b, a non-finite ang_mom_gain or ang_mom_lambda. */
 int osot_dynamics(osot_dyn* d, const osot_dyn_batch* batch, void* hip_stream);
 
 /* ---- batched posture-gradient producer ---------------------------------------------------------------------------

@@ -162,7 +162,13 @@ class DynBatch(C.Structure):
     _fields_ = [("B", C.c_int), ("q", C.c_void_p), ("qdot", C.c_void_p), ("M", C.c_void_p), ("M_stride", C.c_longlong),
                 ("h", C.c_void_p), ("frame_Jdot_qdot", C.c_void_p * KIN_MAX_FRAMES),
                 ("frame_Jdot_qdot_stride", C.c_longlong * KIN_MAX_FRAMES),
-                ("com_Jdot_qdot", C.c_void_p), ("com_Jdot_qdot_stride", C.c_longlong)]
+                ("com_Jdot_qdot", C.c_void_p), ("com_Jdot_qdot_stride", C.c_longlong),
+                ("cmm_lin", C.c_void_p), ("cmm_lin_stride", C.c_longlong), ("cmm_lin_ld", C.c_int),
+                ("cmm_ang", C.c_void_p), ("cmm_ang_stride", C.c_longlong), ("cmm_ang_ld", C.c_int),
+                ("momentum", C.c_void_p), ("momentum_stride", C.c_longlong),
+                ("ang_mom_b", C.c_void_p), ("ang_mom_b_stride", C.c_longlong),
+                ("ang_mom_ref", C.c_void_p), ("ang_mom_rate_ref", C.c_void_p),
+                ("ang_mom_gain", C.c_double * 9), ("ang_mom_lambda", C.c_double)]
 
 
 GRAD_MANIPULABILITY_FRAME, GRAD_MANIPULABILITY_COM, GRAD_MIN_EFFORT = range(3)

@@ -17,7 +17,14 @@
 //   5. h_j = S_j . f_subtree(j);  F_j = Ic_j S_j;  M[i][j] = S_i . F_j where i is an ancestor of j (or j itself), mirrored, zero
 //      elsewhere.  Row r is written by all lanes at once (one coalesced 8 n-byte store); both M[r][c] and M[c][r] evaluate the SAME
 //      fma chain on the same operands, so M is symmetric bit for bit.
-// Algorithmic bytes per instance: reads 8 n (q) + 8 n (qdot), writes 8 n^2 (M) + 8 n (h) + 48 F (frames) + 24 (CoM).
+//  5a. (only in the instantiation with the centroidal momentum outputs) F_j = [n_j; f_j] is the spatial momentum of the subtree joint j
+//      moves per unit qdot_j about the world origin; about the centre of mass c_G it is column j of the centroidal momentum matrix,
+//      rows [linear; angular] = [f_j; n_j - c_G x f_j], world axes (computeCentroidalMomentumMatrix: the reference reads block(0,0,3,n)
+//      as linear, block(3,0,3,n) as angular).  c_G = the last prefix sum of stage 4 / total mass.  momentum = sum_j column_j qdot_j
+//      (wave reduction; computeCentroidalMomentum), ang_mom_b = Ldot_d + lambda K (L_d - L_angular) (acceleration::AngularMomentum with
+//      CMMdot * v = 0 as in the reference).  The cancellation is in n_j - c_G x f_j: both grow with the distance of c_G from the origin.
+// Algorithmic bytes per instance: reads 8 n (q) + 8 n (qdot), writes 8 n^2 (M) + 8 n (h) + 48 F (frames) + 24 (CoM)
+// (+ 48 n (momentum matrix) + 48 (momentum) + 24 (ang_mom_b) when bound).
 #pragma once
 #include <cmath>
 #include <cstring>
@@ -104,8 +111,28 @@ inline int dyn_check_batch(const osot_kin_desc& t, const osot_dyn_batch* b, cons
         if (b->frame_Jdot_qdot_stride[f] < 6) { *why = "frame_Jdot_qdot_stride is below 6"; return OSOT_ERR_INVALID; }
     }
     if (b->com_Jdot_qdot && b->com_Jdot_qdot_stride < 3) { *why = "com_Jdot_qdot_stride is below 3"; return OSOT_ERR_INVALID; }
+    const struct { const double* p; long long stride; int ld; } rows[2] = {{b->cmm_lin, b->cmm_lin_stride, b->cmm_lin_ld},
+                                                                           {b->cmm_ang, b->cmm_ang_stride, b->cmm_ang_ld}};
+    for (int i = 0; i < 2; ++i) {
+        if (!rows[i].p) continue;
+        const long long ld = rows[i].ld ? rows[i].ld : t.n;
+        if (ld < t.n) { *why = "a momentum matrix row length (ld) is below n"; return OSOT_ERR_INVALID; }
+        if (rows[i].stride < 3 * ld) { *why = "a momentum matrix stride is below 3 * ld"; return OSOT_ERR_INVALID; }
+    }
+    if (b->momentum && b->momentum_stride < 6) { *why = "momentum_stride is below 6"; return OSOT_ERR_INVALID; }
+    if (b->ang_mom_b && b->ang_mom_b_stride < 3) { *why = "ang_mom_b_stride is below 3"; return OSOT_ERR_INVALID; }
+    if (!b->ang_mom_b && (b->ang_mom_ref || b->ang_mom_rate_ref)) { *why = "ang_mom_ref / ang_mom_rate_ref without ang_mom_b"; return OSOT_ERR_INVALID; }
+    bool finite = std::isfinite(b->ang_mom_lambda);
+    for (int i = 0; i < 9; ++i) finite = finite && std::isfinite(b->ang_mom_gain[i]);
+    if (!finite) { *why = "ang_mom_gain or ang_mom_lambda is not finite"; return OSOT_ERR_INVALID; }
     return OSOT_OK;
 }
+
+// which instantiation of osot_dyn_kernel a batch runs: DYN_PLAIN has no stage 5a and keeps the early returns of stages 4 and 5 (a
+// batch that binds no centroidal momentum output pays nothing for them), DYN_MOMENTUM forces those stages and adds 5a; DYN_ANY
+// decides per launch (the host build of the tests, which launches osot_dyn_kernel<64>)
+enum { DYN_PLAIN = 0, DYN_MOMENTUM = 1, DYN_ANY = 2 };
+__host__ __device__ inline bool dyn_wants_momentum(const osot_dyn_batch& b) { return b.cmm_lin || b.cmm_ang || b.momentum || b.ang_mom_b; }
 
 // the kinematics batch the kernel hands to kin_instance: same B and q, no output
 inline osot_kin_batch dyn_kin_batch(const osot_dyn_batch& b) {
@@ -150,7 +177,7 @@ __device__ __forceinline__ void ancestor_sum(double* buf, int* Par, const int j,
 // holds the velocities and bias accelerations, then the prefix sums, then F_j = Ic_j S_j
 template <int JMAX> constexpr int dyn_lds_doubles() { return kin_lds_doubles<JMAX>(false) + JMAX * (6 + 16); }
 
-template <int JMAX>
+template <int JMAX, bool MOMENTUM>
 __device__ __forceinline__ void dyn_instance(const DevDyn* __restrict__ D, const osot_dyn_batch& Bt, const osot_kin_batch& Kb,
                                              const long long inst, const bool live, const int j, double* lds) {
     constexpr int TS = OSOT_KIN_TS;
@@ -286,7 +313,7 @@ __device__ __forceinline__ void dyn_instance(const DevDyn* __restrict__ D, const
             for (int i = 0; i < 3; ++i) o[i] = s[i];
         }
     }
-    if (!Bt.M && !Bt.h) return;
+    if (!MOMENTUM && !Bt.M && !Bt.h) return;          // (the momentum outputs need the subtree aggregates and F_j)
     // ---- 4. link wrench; subtree aggregates of [m, m c, Io, wrench] as differences of prefix sums over the depth-first order
     double agg[16];
     {
@@ -349,7 +376,7 @@ __device__ __forceinline__ void dyn_instance(const DevDyn* __restrict__ D, const
     }
     // ---- 5. h_j = S_j . f_subtree(j);  F_j = Ic_j S_j;  the rows of M
     if (Bt.h && valid) Bt.h[inst * n + j] = dot6(S, agg + 10);
-    if (!Bt.M) return;
+    if (!MOMENTUM && !Bt.M) return;
     double F[6];
     {
         const double* hc = agg + 1;
@@ -362,6 +389,61 @@ __device__ __forceinline__ void dyn_instance(const DevDyn* __restrict__ D, const
         F[2] = Ic[2] * S[0] + Ic[4] * S[1] + Ic[5] * S[2] + t1[2];
 #pragma unroll
         for (int i = 0; i < 3; ++i) F[3 + i] = agg[0] * S[3 + i] - t2[i];
+    }
+    // ---- 5a. centroidal momentum: F_j is the spatial momentum of the subtree joint j moves per unit qdot_j, about the world
+    // origin; moved to the centre of mass c_G it is column j of the momentum matrix, [linear f_j; angular n_j - c_G x f_j].
+    // The last prefix sum is the whole tree's [m, m c].
+    if (MOMENTUM) {
+        const double iM = fast_rcp(K->total_mass);
+        double cG[3], cf[3], col[6];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) cG[i] = X[(1 + i) * JMAX + (n - 1)] * iM;
+        cross3(cG, F + 3, cf);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { col[i] = valid ? F[3 + i] : 0.0; col[3 + i] = valid ? F[i] - cf[i] : 0.0; }
+        if (Bt.cmm_lin && valid) {
+            const long long ld = Bt.cmm_lin_ld ? Bt.cmm_lin_ld : n;
+            double* o = Bt.cmm_lin + inst * Bt.cmm_lin_stride + j;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) o[i * ld] = col[i];
+        }
+        if (Bt.cmm_ang && valid) {
+            const long long ld = Bt.cmm_ang_ld ? Bt.cmm_ang_ld : n;
+            double* o = Bt.cmm_ang + inst * Bt.cmm_ang_stride + j;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) o[i * ld] = col[3 + i];
+        }
+        if (Bt.momentum || Bt.ang_mom_b) {
+            double hG[6];
+#pragma unroll
+            for (int i = 0; i < 6; ++i) hG[i] = colsum<JMAX>(col[i] * qd);
+            if (Bt.momentum && j == 0 && live) {
+                double* o = Bt.momentum + inst * Bt.momentum_stride;
+#pragma unroll
+                for (int i = 0; i < 6; ++i) o[i] = hG[i];
+            }
+            if (Bt.ang_mom_b && j == 0 && live) {
+                // acceleration::AngularMomentum: b = Ldot_d + lambda K (L_d - L); no reference = the task's _is_init == false
+                // branch (L_d = L)
+                const double* Kg = Bt.ang_mom_gain;
+                bool unit = true;
+#pragma unroll
+                for (int i = 0; i < 9; ++i) unit = unit && Kg[i] == 0.0;
+                double e[3], rate[3];
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    e[i] = Bt.ang_mom_ref ? Bt.ang_mom_ref[inst * 3 + i] - hG[3 + i] : 0.0;
+                    rate[i] = Bt.ang_mom_rate_ref ? Bt.ang_mom_rate_ref[inst * 3 + i] : 0.0;
+                }
+                double* o = Bt.ang_mom_b + inst * Bt.ang_mom_b_stride;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) {
+                    const double Ke = unit ? e[i] : Kg[3 * i] * e[0] + Kg[3 * i + 1] * e[1] + Kg[3 * i + 2] * e[2];
+                    o[i] = Bt.ang_mom_ref ? rate[i] + Bt.ang_mom_lambda * Ke : rate[i];
+                }
+            }
+        }
+        if (!Bt.M) return;
     }
     wave_sync();                       // everybody has read its prefix sums
 #pragma unroll
@@ -383,12 +465,13 @@ __device__ __forceinline__ void dyn_instance(const DevDyn* __restrict__ D, const
     }
 }
 
-template <int JMAX>
+template <int JMAX, int MODE = DYN_ANY>
 __global__ void __launch_bounds__(64) osot_dyn_kernel(const DevDyn* __restrict__ D, const osot_dyn_batch Bt, const osot_kin_batch Kb) {
     OSOT_STATIC_LDS(double, dyn_lds, dyn_lds_doubles<JMAX>());
     const int j = (int)threadIdx.x;
     const long long inst = (long long)blockIdx.x;
-    dyn_instance<JMAX>(D, Bt, Kb, inst, inst < Bt.B, j, dyn_lds);
+    if (MODE == DYN_MOMENTUM || (MODE == DYN_ANY && dyn_wants_momentum(Bt))) dyn_instance<JMAX, true>(D, Bt, Kb, inst, inst < Bt.B, j, dyn_lds);
+    else dyn_instance<JMAX, false>(D, Bt, Kb, inst, inst < Bt.B, j, dyn_lds);
 }
 
 }  // namespace osot

@@ -205,7 +205,10 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
         OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(pair_dist) OSOT_F(pair_J) OSOT_F(pair_J_stride) OSOT_F(env_pose) OSOT_F(env_pose_stride) OSOT_F(points) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_desc) OSOT_F(inertia) OSOT_F(gravity) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_batch) OSOT_F(B) OSOT_F(q) OSOT_F(qdot) OSOT_F(M) OSOT_F(M_stride) OSOT_F(h) OSOT_F(frame_Jdot_qdot)
-        OSOT_F(frame_Jdot_qdot_stride) OSOT_F(com_Jdot_qdot) OSOT_F(com_Jdot_qdot_stride) OSOT_LAYOUT_END()
+        OSOT_F(frame_Jdot_qdot_stride) OSOT_F(com_Jdot_qdot) OSOT_F(com_Jdot_qdot_stride) OSOT_F(cmm_lin) OSOT_F(cmm_lin_stride)
+        OSOT_F(cmm_lin_ld) OSOT_F(cmm_ang) OSOT_F(cmm_ang_stride) OSOT_F(cmm_ang_ld) OSOT_F(momentum) OSOT_F(momentum_stride)
+        OSOT_F(ang_mom_b) OSOT_F(ang_mom_b_stride) OSOT_F(ang_mom_ref) OSOT_F(ang_mom_rate_ref) OSOT_F(ang_mom_gain)
+        OSOT_F(ang_mom_lambda) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_grad_desc) OSOT_F(n_terms) OSOT_F(kind) OSOT_F(frame) OSOT_F(step) OSOT_F(lambda) OSOT_F(joint_mask)
         OSOT_F(W_diag) OSOT_F(gravity) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_grad_batch) OSOT_F(B) OSOT_F(q) OSOT_F(b) OSOT_F(b_stride) OSOT_F(value) OSOT_LAYOUT_END()
@@ -1256,7 +1259,11 @@ int osot_dynamics(osot_dyn* d, const osot_dyn_batch* b, void* hip_stream) {
     if (b->B == 0) return OSOT_OK;
     DeviceGuard guard(d->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
-    hipLaunchKernelGGL((osot_dyn_kernel<64>), dim3((unsigned)b->B), dim3(64), 0, (hipStream_t)hip_stream, (const DevDyn*)d->dev, *b, dyn_kin_batch(*b));
+    // a batch that binds no momentum output runs the instantiation without stage 5a
+    if (dyn_wants_momentum(*b))
+        hipLaunchKernelGGL((osot_dyn_kernel<64, DYN_MOMENTUM>), dim3((unsigned)b->B), dim3(64), 0, (hipStream_t)hip_stream, (const DevDyn*)d->dev, *b, dyn_kin_batch(*b));
+    else
+        hipLaunchKernelGGL((osot_dyn_kernel<64, DYN_PLAIN>), dim3((unsigned)b->B), dim3(64), 0, (hipStream_t)hip_stream, (const DevDyn*)d->dev, *b, dyn_kin_batch(*b));
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

@@ -44,11 +44,17 @@ class Dynamics:
         except Exception:
             pass
 
-    def batch_args(self, q, qdot=None, M=None, h=None, frame_jdotqdot=None, com_jdotqdot=None):
+    def batch_args(self, q, qdot=None, M=None, h=None, frame_jdotqdot=None, com_jdotqdot=None, cmm_lin=None, cmm_ang=None,
+                   momentum=None, ang_mom_b=None):
         """the osot_dyn_batch of a call (pointers and strides; the tensors must outlive its use).  q, qdot [B][n] (device, qdot
         may be None); M: a tensor whose leading dimension is the batch and whose instances start with the n x n matrix (IdModel.Bm,
         or anything wider: the stride is its row length); h [B][n]; frame_jdotqdot: {frame index: tensor [B][6]} or
-        {frame index: (tensor [B][w], first column)} -- e.g. a task's leaf array p1; com_jdotqdot: tensor [B][>= 3] or (tensor, column)"""
+        {frame index: (tensor [B][w], first column)} -- e.g. a task's leaf array p1; com_jdotqdot: tensor [B][>= 3] or (tensor, column).
+        Centroidal momentum: cmm_lin / cmm_ang: (tensor [B][rows][ld], first row) like frame_J of kinematics.Kinematics (a bare
+        tensor: row 0) -- the 3 linear / angular rows of the momentum matrix, n doubles of each row, e.g. a Generic block's rows of
+        stack.A[k]; momentum: tensor [B][>= 6] or (tensor, column), [linear; angular]; ang_mom_b: dict(out= tensor [B][>= 3] or
+        (tensor, column), ref= L_d [B][3] or None, rate_ref= Ldot_d [B][3] or None, K= 3 x 3 (host) or None for the identity,
+        lam=) -- the b of acceleration::AngularMomentum, Ldot_d + lam K (L_d - L)"""
         B, n = q.shape
         assert n == self.model.n and q.is_contiguous() and q.dtype == torch.float64
         b = abi.DynBatch()
@@ -71,11 +77,37 @@ class Dynamics:
             b.frame_Jdot_qdot[f], b.frame_Jdot_qdot_stride[f] = place(t, 6)
         if com_jdotqdot is not None:
             b.com_Jdot_qdot, b.com_Jdot_qdot_stride = place(com_jdotqdot, 3)
+
+        def rows(t):
+            t, row = t if isinstance(t, tuple) else (t, 0)
+            assert t.is_contiguous() and t.dim() == 3 and t.dtype == torch.float64 and t.shape[0] >= B
+            assert row >= 0 and row + 3 <= t.shape[1] and t.shape[2] >= n
+            return t.data_ptr() + 8 * row * t.shape[2], t.shape[1] * t.shape[2], t.shape[2]
+        if cmm_lin is not None:
+            b.cmm_lin, b.cmm_lin_stride, b.cmm_lin_ld = rows(cmm_lin)
+        if cmm_ang is not None:
+            b.cmm_ang, b.cmm_ang_stride, b.cmm_ang_ld = rows(cmm_ang)
+        if momentum is not None:
+            b.momentum, b.momentum_stride = place(momentum, 6)
+        if ang_mom_b is not None:
+            b.ang_mom_b, b.ang_mom_b_stride = place(ang_mom_b["out"], 3)
+            for key, field in (("ref", "ang_mom_ref"), ("rate_ref", "ang_mom_rate_ref")):
+                r = ang_mom_b.get(key)
+                if r is not None:
+                    assert r.is_contiguous() and r.dtype == torch.float64 and r.shape == (B, 3)
+                    setattr(b, field, r.data_ptr())
+            K = ang_mom_b.get("K")
+            if K is not None:
+                K = np.asarray(K, dtype=float).reshape(9)
+                for i in range(9):
+                    b.ang_mom_gain[i] = float(K[i])
+            b.ang_mom_lambda = float(ang_mom_b.get("lam", 1.0))
         return b
 
-    def forward(self, q, qdot=None, M=None, h=None, frame_jdotqdot=None, com_jdotqdot=None):
-        """osot_dynamics, stream-ordered on torch's current stream"""
-        b = self.batch_args(q, qdot, M, h, frame_jdotqdot, com_jdotqdot)
+    def forward(self, q, qdot=None, M=None, h=None, frame_jdotqdot=None, com_jdotqdot=None, cmm_lin=None, cmm_ang=None,
+                momentum=None, ang_mom_b=None, batch=None):
+        """osot_dynamics, stream-ordered on torch's current stream (batch: a batch_args() result to reuse)"""
+        b = batch if batch is not None else self.batch_args(q, qdot, M, h, frame_jdotqdot, com_jdotqdot, cmm_lin, cmm_ang, momentum, ang_mom_b)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         abi.check(self._lib.osot_dynamics(self._h, C.byref(b), stream), "osot_dynamics")
 
@@ -172,7 +204,7 @@ class IdStep:
         self.Jcom, self.com, self.com_ref = z(B, 3, nv), z(B, 3), None
         # the leaves the producers write straight into: Jdot qdot of the contact tasks and of the CoM task (p1), h of the torque limits (p0)
         (self.p0_l, self.jdq_l, _), (self.p0_r, self.jdq_r, _), (self.p0_com, self.jdq_com, _) = self.dev["task"][0]
-        self.p0_post = self.dev["task"][1][0][0]
+        self.p0_post = self.dev["task"][-1][0][0]                 # (the Postural block is the last level's)
         self.h_u = self.dev["rows"][0][0]
         self.dev["rows"][3] = (self.model.h, self.dev["rows"][3][1], None)
         self.J12 = self.model.Jc.view(B, 12, nv)
@@ -213,6 +245,30 @@ class IdStep:
             self.produce()
         self.consume()
         self.integrate()
+
+
+class IdMomentumStep(IdStep):
+    """IdStep for a stack made by synth.make_coman_id_momentum_stack: the same osot_dynamics launch also writes the rows [A_ang 0] of
+    the acceleration::AngularMomentum block straight into stack.A[level] (row length n = the plan's, the force columns stay zero) and its
+    b = Ldot_d + lambda K (L_d - L) into the block's leaf p0; consume() neither computes nor copies them.  The centroidal momentum of
+    every step lands in self.momentum [B][6].  L_ref / Ldot_ref [B][3] are the caller's (zero here; the reference's task zeroes its own
+    after every update).  On a leaf without state["momentum"] (synth.make_coman_id_stack) only self.momentum is added."""
+
+    def __init__(self, plan, leaf, kin_model, device=0, dt=1.0e-3, gravity=(0.0, 0.0, -9.81)):
+        super().__init__(plan, leaf, kin_model, device, dt, gravity)
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=self.st.device)
+        self.momentum, self.L_ref, self.Ldot_ref = z(self.B, 6), z(self.B, 3), z(self.B, 3)
+        self._extra = dict(momentum=self.momentum)
+        m = leaf["state"].get("momentum")
+        if m is not None:
+            self._extra.update(cmm_ang=(self.st.A[m["level"]], m["row"]),
+                               ang_mom_b=dict(out=self.dev["task"][m["level"]][0][0], ref=self.L_ref, rate_ref=self.Ldot_ref, K=m["K"], lam=m["lam"]))
+
+    def produce(self):
+        self.kin.forward(self.q, frame_J={f: self.model.contact_rows(c) for c, f in enumerate(self.frames)}, com=self.com,
+                         com_J=(self.Jcom, 0))
+        self.dyn.forward(self.q, self.qdot, M=self.model.Bm, h=self.model.h,
+                         frame_jdotqdot={self.frames[0]: self.jdq_l, self.frames[1]: self.jdq_r}, com_jdotqdot=self.jdq_com, **self._extra)
 
 
 def force_gains(J, Bi, Kp, Kd, p0, rows, f_virtual=None, a_ref=None):

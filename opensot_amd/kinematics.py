@@ -334,9 +334,11 @@ class Kinematics:
         except Exception:
             pass
 
-    def forward(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None):
-        """osot_kinematics for the batch `batch_args` describes, stream-ordered on torch's current stream"""
-        kb = self.batch_args(q, frame_pose, frame_J, com, com_J, pair_dist, pair_J, env_pose, points)
+    def forward(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None,
+                batch=None):
+        """osot_kinematics for the batch `batch_args` describes, stream-ordered on torch's current stream (batch: a batch_args()
+        result to reuse)"""
+        kb = batch if batch is not None else self.batch_args(q, frame_pose, frame_J, com, com_J, pair_dist, pair_J, env_pose, points)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         abi.check(self._lib.osot_kinematics(self._h, C.byref(kb), stream), "osot_kinematics")
 

@@ -1116,3 +1116,103 @@ def bind_posture_gradient(stack, grad, leaf, kin=None):
         dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
         kb = kin.batch_args(q, **kw)
     return dev, grad.batch_args(q, b=out), kb, q
+
+
+# ---- the momentum tasks: their rows come from the dynamics producer's centroidal momentum matrix ----------------------------------------
+def make_coman_momentum_stack(B, seed=None, tree=None, inertia=None, momentum=True, linear_momentum=False, swing=0.3, postural_lam=0.1,
+                              dT=0.01, eps_factor=1e6):
+    """`((l_sole + r_sole + com) / angular_momentum / postural) << joint_limits << velocity_limits` on the reference's COMAN with its
+    inertia fixture: the soles and the CoM hold their first poses, tasks::velocity::AngularMomentum (AngularMomentum.cpp:44-51: A = the
+    angular rows of the centroidal momentum matrix, b = the desired momentum, here zero) sits above a Postural task whose reference
+    swings the arms and the waist by up to `swing` radians -- so the bottom level asks for angular momentum and the level above it
+    refuses.  The momentum task is an OSOT_TASK_GENERIC block of 3 stored rows that the DYNAMICS producer writes (osot_dyn_batch.cmm_ang)
+    and whose b is the leaf p0; poses, Jacobians and the CoM are left for the kinematics producer.
+    momentum=False drops that level and changes nothing else.  linear_momentum=True replaces the CoM task by the 3-row
+    tasks::velocity::LinearMomentum block (LinearMomentum.cpp:43-48: A = the linear rows, b = 0) in the same rows of A_0.
+    Returns (plan, leaf, model); leaf["state"] = q0, q_ref, momentum = (level, first row) or None, linear_momentum = (0, 12) or None.
+    bind_momentum() wires the device tensors."""
+    import json
+    import os
+    rng = np.random.default_rng(19000 if seed is None else seed)
+    here = os.path.dirname(os.path.abspath(__file__))
+    model, q0, qmin, qmax = _coman_bent(rng, B, tree)
+    model.inertia = np.array(json.load(open(inertia or os.path.join(os.path.dirname(here), "tests", "golden", "coman_inertia.json")))["inertia"],
+                             dtype=float).reshape(model.n, 6)
+    n, ix = model.n, model.names.index
+    upper = list(range(ix("WaistLat"), ix("RHipSag")))          # waist and arms
+    q_ref = q0.copy()
+    q_ref[:, upper] += rng.uniform(-swing, swing, (B, len(upper)))
+    q_ref = np.clip(q_ref, qmin + 1e-3, qmax - 1e-3)
+    z = lambda *sh: np.zeros(sh)
+    third = Task(abi.TASK_GENERIC, 3, name="linear_momentum") if linear_momentum else Task(abi.TASK_COM, 3, lam=1.0, name="com")
+    levels = [[Task(abi.TASK_CARTESIAN, 6, lam=1.0, name="l_sole"), Task(abi.TASK_CARTESIAN, 6, lam=1.0, name="r_sole"), third]]
+    A = [z(B, 15, n)]
+    tleaf = [[(z(B, 12), z(B, 12), None), (z(B, 12), z(B, 12), None), (z(B, 3), None, None) if linear_momentum else (z(B, 3), z(B, 3), None)]]
+    if momentum:
+        levels.append([Task(abi.TASK_GENERIC, 3, name="angular_momentum")])
+        A.append(z(B, 3, n))
+        tleaf.append([(z(B, 3), None, None)])
+    levels.append([Task(abi.TASK_POSTURAL, n, lam=postural_lam, name="postural")])
+    A.append(None)
+    tleaf.append([(q0.copy(), q_ref, None)])
+    bounds = [Bound(abi.BOUND_JOINT_LIMITS, scaling=0.2, name="joint_limits"), Bound(abi.BOUND_VELOCITY_LIMITS, dT=dT, name="velocity_limits")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": A, "task": tleaf,
+            "bound": [(q0.copy(), np.tile(qmin, (B, 1)), np.tile(qmax, (B, 1))), (np.full((B, n), np.pi / 2.0), None, None)],
+            "rows": [], "C": [],
+            "state": {"q0": q0, "q_ref": q_ref, "frames": (model.frame_index("l_sole"), model.frame_index("r_sole")),
+                      "momentum": (1, 0) if momentum else None, "linear_momentum": (0, 12) if linear_momentum else None}}
+    return plan, leaf, model
+
+
+def bind_momentum(stack, kin, dyn, leaf):
+    """wire make_coman_momentum_stack to the device: ONE q tensor is the input of both producers, the Postural block's actual posture and
+    the joint limits' q.  The kinematics producer writes the soles' poses into the Cartesian tasks' p0, their Jacobians and the CoM's
+    into stack.A[0]; the dynamics producer writes the angular rows of the momentum matrix into stack.A[level] at the momentum block's
+    rows (and the linear rows into stack.A[0] where the stack has the LinearMomentum block).  The references of the soles and of the CoM
+    are the first posture's; the b of the momentum blocks are their leaf p0 (zero; the caller owns them).
+    -> (dev_leaf, kin_batch, dyn_batch or None, q)"""
+    import torch
+    B, s = leaf["B"], leaf["state"]
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q = torch.as_tensor(s["q0"], **f64).contiguous()
+    frames = s["frames"]
+    poses = [dev["task"][0][i][0] for i in range(2)]
+    kw = dict(frame_pose={f: poses[i] for i, f in enumerate(frames)}, frame_J={f: (stack.A[0], 6 * i) for i, f in enumerate(frames)})
+    if s["linear_momentum"] is None:
+        kw.update(com=dev["task"][0][2][0], com_J=(stack.A[0], 12))
+    kin.forward(q, **kw)
+    for i in range(2):
+        dev["task"][0][i] = (poses[i], poses[i].clone(), None)
+    if s["linear_momentum"] is None:
+        dev["task"][0][2] = (kw["com"], kw["com"].clone(), None)
+    last = len(dev["task"]) - 1
+    dev["task"][last][0] = (q, dev["task"][last][0][1], None)
+    dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
+    dk = {}
+    if s["momentum"] is not None:
+        dk["cmm_ang"] = (stack.A[s["momentum"][0]], s["momentum"][1])
+    if s["linear_momentum"] is not None:
+        dk["cmm_lin"] = (stack.A[s["linear_momentum"][0]], s["linear_momentum"][1])
+    db = None
+    if dk:
+        dyn.forward(q, **dk)
+        db = dyn.batch_args(q, **dk)
+    return dev, kin.batch_args(q, **kw), db, q
+
+
+def make_coman_id_momentum_stack(B, seed=None, tree=None, inertia=None, eps_factor=1e6):
+    """make_coman_id_stack with tasks::acceleration::AngularMomentum (AngularMomentum.cpp:31-60) between the contact / CoM level and the
+    Postural one: an OSOT_TASK_GENERIC block of 3 rows [A_ang 0] of row length n = 47 that the dynamics producer writes into the
+    zero-initialised A_1 (osot_dyn_batch.cmm_ang with ld = n), its b = Ldot_d + lambda K (L_d - L) formed by the same launch into the
+    block's leaf p0 (osot_dyn_batch.ang_mom_b) with lambda = 1, K = I, L_d = 0, Ldot_d = 0.
+    Returns (plan, leaf, model) for dynamics.IdMomentumStep; leaf["state"]["momentum"] = dict(level, row, lam, K)."""
+    plan0, leaf, model = make_coman_id_stack(B, seed=seed, tree=tree, inertia=inertia, eps_factor=eps_factor)
+    n = plan0.n
+    levels = [plan0.levels[0], [Task(abi.TASK_GENERIC, 3, name="angular_momentum")], plan0.levels[1]]
+    plan = StackPlan(n=n, levels=levels, bounds=[], rowblocks=plan0.rowblocks, eps_abs=plan0.eps_abs)
+    leaf["A"] = [leaf["A"][0], np.zeros((B, 3, n)), None]
+    leaf["task"] = [leaf["task"][0], [(np.zeros((B, 3)), None, None)], leaf["task"][1]]
+    leaf["state"]["momentum"] = dict(level=1, row=0, lam=1.0, K=np.eye(3))
+    return plan, leaf, model
