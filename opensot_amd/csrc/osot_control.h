@@ -72,7 +72,10 @@ __global__ void __launch_bounds__(64, (NP == 32 ? OSOT_WAVES32 : (NP == 40 ? OSO
         update_body(OSOT_KERNARG_PTR(DevUpdate, U), inst, (int)tid, osot_smem);
         workgroup_fence();
         __syncthreads();
-        cascade_body<NP, false, EXTRA, BOX>(P, D, inst, (int)tid, osot_smem);
+        if constexpr (NP == 32 && !EXTRA && BOX) {
+            if (lean_plan(P, D)) cascade_body<32, false, false, true, true>(P, D, inst, (int)tid, osot_smem);
+            else cascade_body<32, false, false, true, false>(P, D, inst, (int)tid, osot_smem);
+        } else cascade_body<NP, false, EXTRA, BOX>(P, D, inst, (int)tid, osot_smem);
         const int n = P.n, i = (int)tid;
         if (F.q_int && i < n) F.q_int[inst * n + i] += D.dq[inst * n + i];       // q += dq (the lane that stored dq[i] reads it back: its own store)
         if (ROLL && F.dq_steps && i < n) F.dq_steps[((long long)t * D.B + inst) * n + i] = D.dq[inst * n + i];

@@ -103,6 +103,22 @@ struct DevBatch {
 };
 static_assert(std::is_trivially_copyable<DevPlan>::value && std::is_trivially_copyable<DevBatch>::value, "kernel arguments, zeroed with memset");
 
+// LEAN plans (full-width, box-only: BASELINE configs 2 and 3 at 32 variables): what the lean path of cascade_body<32, ., false, true>
+// takes for granted at compile time (osot_qp_core.h, LeanRows).  One wave-uniform test of the kernel arguments per launch; the
+// other branch is the body as it is for every other plan.  Host-checkable: the emulation runs the same test.
+// -DOSOT_NO_LEAN (developer builds, tools/build_variant.sh): never lean -- the other arm of an A/B from one tree.
+__host__ __device__ inline bool lean_plan(const DevPlan& P, const DevBatch& D) {
+#ifdef OSOT_NO_LEAN
+    (void)P; (void)D;
+    return false;
+#else
+    bool ok = P.n == 32 && P.nc == 0 && P.nblocks == 0 && D.b_reg == nullptr && D.l != nullptr && D.u != nullptr && D.hot == nullptr;
+    for (int k = 0; k < P.L; ++k)
+        ok = ok && ((P.active_mask >> k) & 1u) && D.c[k] == nullptr && D.w[k] != nullptr && D.WA[k] == nullptr && P.inactive[k] == 0u;
+    return ok;
+#endif
+}
+
 // Row table of level k (LDS): [ global C rows ; A_0 ; ... ; A_{k-1} ]  (iHQP.cpp:282-333).  The C entries are
 // filled once per instance, the optimality entries of level j are appended when level j has been solved
 // (lo = up = A_j x_j, iHQP.cpp:164-170; an inactive level contributes 0*x in [-1,1], iHQP.cpp:301-309).
@@ -110,10 +126,12 @@ static_assert(std::is_trivially_copyable<DevPlan>::value && std::is_trivially_co
 // one carries none of that code (registers, scalar loads, branches) -- launches pick it whenever the plan has no dense-weight
 // level and every task is active
 // BOX: plans without constraint rows (the bounds are the only inequalities; see gi_inequalities)
-template <int NP, bool PROF, bool EXTRA, bool BOX = false>
+// LEAN: a lean_plan (above) -- no padding, no row table, none of the code for what such a plan does not have
+template <int NP, bool PROF, bool EXTRA, bool BOX = false, bool LEAN = false>
 __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D, const long long inst, const int lane, char* osot_smem) {
+    static_assert(!LEAN || (NP == 32 && !EXTRA && BOX), "the lean path is a path of the 32-lane BOX instantiation");
     constexpr int HV = WaveCtx<NP>::HV, S = WaveCtx<NP>::S;
-    const int n = P.n;
+    const int n = LEAN ? 32 : P.n;
     double* base = reinterpret_cast<double*>(osot_smem);
     WaveCtx<NP> w;
     w.c = WaveCtx<NP>::col_of(lane); w.h = WaveCtx<NP>::half_of(lane); w.n = n;
@@ -132,17 +150,17 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
     w.safe_row = reinterpret_cast<unsigned long long>(D.dq + inst * n);   // n readable doubles (value is discarded)
     w.rsrc = reinterpret_cast<signed char*>(w.eqlist + P.lds_rows_cap);
     const int c = w.c, h = w.h;
-    const bool valid = c < n;
+    const bool valid = LEAN || c < n;
     // zero the matrices once: the padding beyond n stays zero for the whole kernel
     for (int e = lane; e < WaveCtx<NP>::LDS_DOUBLES; e += 64) base[e] = 0.0;
     wave_sync();
 
-    const bool has_box = D.l != nullptr;
+    const bool has_box = LEAN || D.l != nullptr;
     double lb = (has_box && valid) ? D.l[inst * n + c] : -INFINITY;   // (a level may relax a bound it accepted as satisfied)
     double ub = (has_box && valid) ? D.u[inst * n + c] : INFINITY;
 
     // global rows: bounds and row addresses, lane = row
-    for (int j = 0; j < P.nblocks; ++j) {
+    for (int j = 0; j < (LEAN ? 0 : P.nblocks); ++j) {
         for (int q = lane; q < P.blk_rows[j]; q += 64) {
             const int r = P.blk_off[j] + q;
             w.rlo[r] = clamp_inf(D.lo[inst * P.nc + r]);
@@ -153,11 +171,11 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
             w.rsrc[r] = -1;
         }
     }
-    wave_sync();
+    if constexpr (!LEAN) wave_sync();
 
     // regularisation task (same for every level): its diagonal joins eps, its linear term joins g
     const bool regd = EXTRA && P.reg_dense && D.b_reg != nullptr;       // stored Jacobian: added row by row in the H build
-    const bool regc = D.b_reg != nullptr && !regd && c < P.reg_rows;
+    const bool regc = !LEAN && D.b_reg != nullptr && !regd && c < P.reg_rows;
     const double greg = regc ? -P.reg_w * D.b_reg[inst * P.reg_rows + c] : 0.0;
     const double dreg = regc ? P.reg_w : 0.0;
 
@@ -170,7 +188,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
     if (PROF) for (int i = 0; i < PH_COUNT; ++i) prof[i] = 0;
     const long long t_begin = PROF ? (long long)clock64() : 0;
     for (int k = 0; k < P.L; ++k) {
-        if (!((P.active_mask >> k) & 1u)) {
+        if (!LEAN && !((P.active_mask >> k) & 1u)) {
             // inactive level: its optimality rows are 0*x in [-1, 1] (iHQP.cpp:301-309): never binding
             if (k + 1 < P.L) {
                 const int off = P.nc + P.optoff[k];
@@ -184,7 +202,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
         }
         // task-local row blocks (Task::getConstraints(), iHQP.cpp:190, 282-287): real bounds at their own level,
         // "absent" (infinite bounds: never scanned as violated, never an equality) at every other level
-        for (int j = 0; j < P.nblocks; ++j) {
+        for (int j = 0; j < (LEAN ? 0 : P.nblocks); ++j) {
             if (P.blk_level[j] == 0) continue;
             const bool on = P.blk_level[j] - 1 == k;
             for (int q = lane; q < P.blk_rows[j]; q += 64) {
@@ -201,7 +219,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
             w.c = WaveCtx<NP>::col_of(l2); w.h = WaveCtx<NP>::half_of(l2);
         }
         const int c = w.c, h = w.h;
-        const bool valid = c < n;
+        const bool valid = LEAN || c < n;
         const int m = P.m[k], ma = P.ma[k];
         // hot start (osot_solver_set_hotstart, default off) lives in the EXTRA instantiation only: the plain one carries none of its
         // code (its branches at the top of every active-set trip, a vector and a handful of scalar registers: measured +4 %)
@@ -209,7 +227,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
         const int hotcode = hotk ? hotk[c] : -1;   // (requested here: the answer is not needed before the inequality loop)
         const double* Ak = D.A[k] ? D.A[k] + inst * ma * n : nullptr;
         const double* bk = D.b[k] + inst * m;
-        const double* wk = D.w[k] ? D.w[k] + inst * m : nullptr;
+        const double* wk = (LEAN || D.w[k]) ? D.w[k] + inst * m : nullptr;
         // non-diagonal W_k: left operand W_k A_k and W_k b_k come from the update kernel (stored rows only: an implicit
         // Postural block keeps its diagonal weights w)
         const bool dense = EXTRA && D.WA[k] != nullptr;
@@ -223,7 +241,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
                 off = off || (((inact >> j) & 1u) && r >= P.task_off[k][j] && r < P.task_off[k][j + 1]);
             return off;
         };
-        auto wrow = [&](int r) -> double { return (inact && row_off(r)) ? 0.0 : (wk ? wk[r] : 1.0); };
+        auto wrow = [&](int r) -> double { return (inact && row_off(r)) ? 0.0 : ((LEAN || wk) ? wk[r] : 1.0); };
         double g = 0.0, hdiag = 0.0;
         const bool diag_h = (ma == 0) && !regd;
         double hacc[NP / HV];
@@ -279,13 +297,13 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
                 lowrank = true;
                 const int npost = m - ma;
                 const bool postc = valid && c < npost;
-                const double wpost = postc ? (wk ? wk[ma + c] : 1.0) : 0.0;
-                double cvec = ((D.c[k] && valid) ? D.c[k][inst * n + c] : 0.0) + greg;
+                const double wpost = postc ? ((LEAN || wk) ? wk[ma + c] : 1.0) : 0.0;
+                double cvec = ((!LEAN && D.c[k] && valid) ? D.c[k][inst * n + c] : 0.0) + greg;
                 if (postc) cvec -= wpost * bk[ma + c];
-                const bool has_c = D.c[k] != nullptr || npost > 0 || D.b_reg != nullptr;
-                if (ma <= 3) lowrank_prepare<NP, 3>(w, Ak, bk, wk, ma, P.eps_abs + wpost + dreg, cvec, has_c, xprep);
-                else if (kLowRankMax <= 4 || ma <= 4) lowrank_prepare<NP, (kLowRankMax < 4 ? kLowRankMax : 4)>(w, Ak, bk, wk, ma, P.eps_abs + wpost + dreg, cvec, has_c, xprep);
-                else lowrank_prepare<NP, kLowRankMax>(w, Ak, bk, wk, ma, P.eps_abs + wpost + dreg, cvec, has_c, xprep);
+                const bool has_c = LEAN ? npost > 0 : (D.c[k] != nullptr || npost > 0 || D.b_reg != nullptr);
+                if (ma <= 3) lowrank_prepare<NP, 3, LEAN>(w, Ak, bk, wk, ma, P.eps_abs + wpost + dreg, cvec, has_c, xprep);
+                else if (kLowRankMax <= 4 || ma <= 4) lowrank_prepare<NP, (kLowRankMax < 4 ? kLowRankMax : 4), LEAN>(w, Ak, bk, wk, ma, P.eps_abs + wpost + dreg, cvec, has_c, xprep);
+                else lowrank_prepare<NP, kLowRankMax, LEAN>(w, Ak, bk, wk, ma, P.eps_abs + wpost + dreg, cvec, has_c, xprep);
             }
         }
         if (lowrank || dense_done) {
@@ -314,11 +332,11 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
                 const int r = r0 + tq;
                 const bool in = r < ma && !(inact && row_off(r));
                 const int rr = (r < ma) ? r : ma - 1;
-                const int c0 = (ta < n) ? ta : 0, c1 = (16 + ta < n) ? 16 + ta : 0;
+                const int c0 = (LEAN || ta < n) ? ta : 0, c1 = (LEAN || 16 + ta < n) ? 16 + ta : 0;
                 const double v0 = Ak[rr * n + c0];
                 const double v1 = Ak[rr * n + c1];
-                a0 = (in && ta < n) ? v0 : 0.0;
-                a1 = (in && 16 + ta < n) ? v1 : 0.0;
+                a0 = (in && (LEAN || ta < n)) ? v0 : 0.0;
+                a1 = (in && (LEAN || 16 + ta < n)) ? v1 : 0.0;
                 if (dense) {
                     gb = Wbk[rr];
                     const double u0 = WAk[rr * n + c0], u1 = WAk[rr * n + c1];
@@ -327,7 +345,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
                 } else {
                     const int src4 = (rr - bw_base) << 2;
                     gb = permute_f64(bw_b, src4);
-                    const double wv = wk ? permute_f64(bw_w, src4) : 1.0;
+                    const double wv = (LEAN || wk) ? permute_f64(bw_w, src4) : 1.0;
                     l0 = wv * a0; l1 = wv * a1;
                 }
             };
@@ -341,7 +359,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
                 if (!dense && (rb & 63) == 0) {          // rows rb .. rb + 63 of b and w, lane = row
                     const int rl = rb + lane;
                     bw_b = (rl < ma) ? bk[rl] : 0.0;
-                    bw_w = (wk && rl < ma) ? wk[rl] : 1.0;
+                    bw_w = ((LEAN || wk) && rl < ma) ? wk[rl] : 1.0;
                     bw_base = rb;
                 }
                 double ca0[HBD], ca1[HBD], cl0[HBD], cl1[HBD], cbr[HBD];
@@ -391,9 +409,9 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
 #pragma unroll
             for (int I = 0; I < 2; ++I) {
                 const int i = 16 * I + ta;    // diagonal element (i, i) lives in tile (I, I) where a == q + 4 r
-                double dv = (i < n) ? P.eps_abs : 1.0;
+                double dv = (LEAN || i < n) ? P.eps_abs : 1.0;
                 if (i < npost) dv += wrow(ma + i);
-                if (D.b_reg && !regd && i < P.reg_rows) dv += P.reg_w;
+                if (!LEAN && D.b_reg && !regd && i < P.reg_rows) dv += P.reg_w;
 #pragma unroll
                 for (int r = 0; r < 4; ++r) Ht[I][I][r] += (ta == tq + 4 * r) ? dv : 0.0;
             }
@@ -529,8 +547,8 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
             hdiag = wi + P.eps_abs + dreg;
             g = inb ? -wi * bk[c] : 0.0;
         }
-        if (D.c[k] && valid && !lowrank) g += D.c[k][inst * n + c];
-        if (!lowrank) g += greg;
+        if (!LEAN && D.c[k] && valid && !lowrank) g += D.c[k][inst * n + c];
+        if (!lowrank) g += greg;   // (LEAN: greg = 0.0, and the addition stays: -0.0 + 0.0 is +0.0, the general body's bits)
 
         const int nrows = P.nc + P.optoff[k];
         int iters = 0;
@@ -541,9 +559,11 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
                                                                    has_box, lb, ub, P.max_iter, any, x, x, iters, prof, slack,
                                                                    lowrank, xprep, hotcode, hotk, dn_rank, dn_neq, dn_x, dn_hinv);
         } else {          // NP = 32: inlined as well (as a CALL the solver spends ~50 % more cycles: the tiles travel through scratch)
-            OSOT_ALWAYS_INLINE_CALL st = gi_solve<NP, PROF, BOX>(w, nrows, g, diag_h, hdiag, hacc,
+            // (LEAN: the rows are the optimality rows of the levels 0 .. k-1, found from the plan -- no table)
+            const LeanRows lr = {P.optoff, P.m, P.ma, D.A, inst, k};
+            OSOT_ALWAYS_INLINE_CALL st = gi_solve<NP, PROF, BOX, LEAN>(w, nrows, g, diag_h, hdiag, hacc,
                                            has_box, lb, ub, P.max_iter, any, x, x, iters, prof, slack, lowrank, xprep,
-                                           hotcode, hotk);
+                                           hotcode, hotk, -1, 0, 0.0, 0.0, lr);
         }
         if (PROF) ph_t0_ = (long long)clock64();
 #ifdef OSOT_TRACE_LEVELS   // developer knob (emulator builds): one line per (instance, level) with the level's trip count
@@ -556,7 +576,7 @@ __device__ __forceinline__ void cascade_body(const DevPlan& P, const DevBatch& D
         // optimality rows A_k x = A_k x_k for the lower levels (iHQP.cpp:164-170) -> row table.  Only the
         // row addresses and x_k are recorded: the right-hand side is taken relative to the current iterate,
         // a'(x_k - x), when the row is added, so A_k is not re-read and no reduction pass is needed here.
-        if (k + 1 < P.L) {
+        if (!LEAN && k + 1 < P.L) {
             const int off = P.nc + P.optoff[k];
             for (int q = lane; q < m; q += 64) {
                 const bool void_row = inact && row_off(q);   // inactive task: 0 x = 0 (Task.h:383-387), i.e. no row
@@ -602,7 +622,10 @@ __global__ void __launch_bounds__(64, (NP == 32 ? OSOT_WAVES32 : (NP == 40 ? OSO
     OSOT_DYNAMIC_LDS(osot_smem);
     const long long inst = dispatch_instance(D, osot_smem);
     if (inst < 0) return;
-    cascade_body<NP, PROF, EXTRA, BOX>(P, D, inst, (int)threadIdx.x, osot_smem);
+    if constexpr (NP == 32 && !EXTRA && BOX) {
+        if (lean_plan(P, D)) cascade_body<32, PROF, false, true, true>(P, D, inst, (int)threadIdx.x, osot_smem);
+        else cascade_body<32, PROF, false, true, false>(P, D, inst, (int)threadIdx.x, osot_smem);
+    } else cascade_body<NP, PROF, EXTRA, BOX>(P, D, inst, (int)threadIdx.x, osot_smem);
 }
 
 // Longest-first dispatch.  One wavefront solves one instance and an MI355X holds 2048 of them at a time, so a
@@ -1507,7 +1530,10 @@ __global__ void __launch_bounds__(64, (NP == 32 ? OSOT_WAVES32 : (NP == 40 ? OSO
     workgroup_fence();      // the update's global stores are visible to the cascade's loads (same workgroup)
     __syncthreads();
     const long long tc1 = D.prof ? (long long)clock64() : 0;
-    cascade_body<NP, false, EXTRA, BOX>(P, D, inst, (int)threadIdx.x, osot_smem);
+    if constexpr (NP == 32 && !EXTRA && BOX) {
+        if (lean_plan(P, D)) cascade_body<32, false, false, true, true>(P, D, inst, (int)threadIdx.x, osot_smem);
+        else cascade_body<32, false, false, true, false>(P, D, inst, (int)threadIdx.x, osot_smem);
+    } else cascade_body<NP, false, EXTRA, BOX>(P, D, inst, (int)threadIdx.x, osot_smem);
     if (D.prof && threadIdx.x == 0) {   // diagnostic (osot_solver_profile_cycle): shader-clock cycles of the two halves
         D.prof[inst * 4] = tc1 - tc0;
         D.prof[inst * 4 + 1] = (long long)clock64() - tc1;

@@ -130,6 +130,40 @@ __device__ __forceinline__ double row_elem(const WaveCtx<NP>& w, int r, int col)
     return unit ? uv : ((col < w.n) ? v : 0.0);
 }
 
+// LEAN (NP = 32; osot_kernels.h, lean_plan): the instantiation for full-width, box-only plans -- n = 32 exactly, no constraint rows,
+// every level active, diagonal weights, no linear term, no regularisation task.  Two things are then known at compile time:
+//   * there is no padding: every "c < n" is true, every clamped column index is the index itself;
+//   * the row table is IMPLICIT: the rows a level sees are exactly the optimality rows of the levels above it, in the table's
+//     order -- row optoff[j] + q is row q of level j: the stored row A_j + q n, or the unit row e_(q - ma_j) of a Postural block; its
+//     bounds are lo = up = 0, every row is an equality that x_prev satisfies (rsrc = j >= 0).  No rlo / rup / rptr / rowstate /
+//     eqlist / rsrc traffic, no classification; a row's address comes from (j, q).
+// The arithmetic, its order and the order of the rows are those of the general body: the results are the same bits.
+struct LeanRows {
+    const int* optoff;          // the plan's prefix sums of m[], m[] and ma[]
+    const int* m;
+    const int* ma;
+    const double* const* A;     // the batch's level Jacobians (null where ma = 0)
+    long long inst;
+    int nlev;                   // levels above the one being solved: rows 0 .. optoff[nlev] - 1 are visible
+};
+// row `row` of the implicit table: the address of its 32 doubles (safe for a unit row) and the unit row's column (-1: stored)
+__device__ __forceinline__ void lean_row(const LeanRows& lr, int row, unsigned long long safe, unsigned long long& addr, int& ucol) {
+    addr = safe; ucol = -1;
+    for (int j = 0; j < lr.nlev; ++j) {
+        const int q = row - lr.optoff[j], maj = lr.ma[j];
+        const bool in = q >= 0 && q < lr.m[j];
+        const bool stored = q < maj;
+        const unsigned long long a = reinterpret_cast<unsigned long long>(lr.A[j]) + (unsigned long long)(((lr.inst * maj + q) * 32) * 8);
+        if (in) { addr = stored ? a : safe; ucol = stored ? -1 : q - maj; }
+    }
+}
+__device__ __forceinline__ double lean_row_elem(const LeanRows& lr, int row, unsigned long long safe, int col) {   // (row is wave-uniform)
+    unsigned long long addr; int ucol;
+    lean_row(lr, row, safe, addr, ucol);
+    const double v = OSOT_GLOBAL_F64(addr)[col];
+    return (ucol >= 0) ? ((col == ucol) ? 1.0 : 0.0) : v;
+}
+
 __device__ __forceinline__ double clamp_inf(double v) {
     return v < -kInfty ? -kInfty : (v > kInfty ? kInfty : v);
 }
@@ -387,15 +421,15 @@ __device__ __forceinline__ void drop_constraint(const WaveCtx<NP>& w, int qq, in
 // SKIP (round 6, nullspace_dense_wide's borrowed context: a reduced Hessian of 14 .. 24 columns): panels that lie wholly in the identity
 // padding beyond n run under a uniform guard -- the padding factorises to itself, its off-diagonal entries are zero, so skipping them is
 // exact (factor_tiles_wide does the same).  The cascade's own calls keep SKIP = false: no branch in the headline's panel sequence.
-template <bool TT = false, bool SKIP = false>
+template <bool TT = false, bool SKIP = false, bool LEAN = false>
 __device__ inline int factor_tiles32(const WaveCtx<32>& w, double (&Hf)[16], double g, double& x_out, long long* tt = nullptr) {
     long long tt0 = TT ? (long long)clock64() : 0;
 #define OSOT_TT(i) do { if (TT) { const long long t_ = (long long)clock64(); tt[i] += t_ - tt0; tt0 = t_; } } while (0)
     constexpr int S = WaveCtx<32>::S;
-    const int c = w.c, n = w.n;
+    const int c = w.c, n = LEAN ? 32 : w.n;
     const int lane = c + 32 * w.h;
     const int ta = lane & 15, tq = lane >> 4;
-    const bool valid = c < n;
+    const bool valid = LEAN || c < n;
     double* PB = w.M1;   // [4][32] staging of the finished panel: PB[q * 32 + i] = L[i][4p + q]
     double* M2 = w.M2;
     double rhs = valid ? -g : 0.0;   // forward substitution, lane c = row c (replicated over the halves)
@@ -676,14 +710,14 @@ enum { PH_HBUILD = 0, PH_CHOL = 1, PH_INV = 2, PH_SUBST = 3, PH_EQ = 4, PH_INEQ 
 // Returns the rank (= number of equality positions in the working set), or -1 if nf > kNullMax (caller then
 // takes the generic path; M2 = JT is as it was on entry in that case).
 constexpr int kNullMax = 8;
-template <bool PROF>
+template <bool PROF, bool LEAN = false>
 __device__ inline int nullspace_equalities32(const WaveCtx<32>& w, int n_eq, double hdiag, double g, double xprev,
-                                             double& x_out, long long* prof) {
+                                             double& x_out, long long* prof, const LeanRows& lr = LeanRows()) {
     OSOT_SUB_BEGIN();
     constexpr int S = WaveCtx<32>::S;
-    const int c = w.c, h = w.h, n = w.n;
+    const int c = w.c, h = w.h, n = LEAN ? 32 : w.n;
     const int lane = c + 32 * h;
-    const bool valid = c < n;
+    const bool valid = LEAN || c < n;
     double* M2 = w.M2;
     // ---- E -> registers in the ACCUMULATOR-TILE layout of v_mfma_f64_16x16x4: lane l = (ta, tq) = (l & 15, l >> 4), tile
     // (I, C) element r holds E[16 I + tq + 4 r][16 C + ta] (the layout of factor_tiles32).  All sixteen row pointers first,
@@ -692,22 +726,24 @@ __device__ inline int nullspace_equalities32(const WaveCtx<32>& w, int n_eq, dou
     v4f64 Et[4];   // Et[2 I + C]
     double emax = 0.0;
     {
-        unsigned long long rp[8];
+        unsigned long long rp[8];   // the row's address (LEAN: safe_row for a unit row), or its table entry
+        int uc[8];                  // LEAN: the unit row's column, -1 for a stored row
         double ld[16];
 #pragma unroll
         for (int I = 0; I < 2; ++I)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = 16 * I + tq + 4 * r;
-                rp[4 * I + r] = w.rptr[w.eqlist[(row < n_eq) ? row : 0]];
+                if constexpr (LEAN) lean_row(lr, (row < n_eq) ? row : 0, w.safe_row, rp[4 * I + r], uc[4 * I + r]);   // (the list is the table itself)
+                else { rp[4 * I + r] = w.rptr[w.eqlist[(row < n_eq) ? row : 0]]; uc[4 * I + r] = 0; }
             }
-        const int c0 = (ta < n) ? ta : 0, c1 = (16 + ta < n) ? 16 + ta : 0;
+        const int c0 = (LEAN || ta < n) ? ta : 0, c1 = (LEAN || 16 + ta < n) ? 16 + ta : 0;
 #pragma unroll
         for (int I = 0; I < 2; ++I)
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const unsigned long long pr = rp[4 * I + r];
-                const auto* base = OSOT_GLOBAL_F64((pr & 1ull) ? w.safe_row : pr);
+                const auto* base = OSOT_GLOBAL_F64((!LEAN && (pr & 1ull)) ? w.safe_row : pr);
                 ld[8 * I + 2 * r] = base[c0];
                 ld[8 * I + 2 * r + 1] = base[c1];
             }
@@ -717,13 +753,13 @@ __device__ inline int nullspace_equalities32(const WaveCtx<32>& w, int n_eq, dou
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const unsigned long long pr = rp[4 * I + r];
-                const bool unit = (pr & 1ull) != 0ull;
-                const int ucol = (int)(pr >> 1);
+                const bool unit = LEAN ? (uc[4 * I + r] >= 0) : ((pr & 1ull) != 0ull);
+                const int ucol = LEAN ? uc[4 * I + r] : (int)(pr >> 1);
                 const bool in = (16 * I + tq + 4 * r) < n_eq;
 #pragma unroll
                 for (int C = 0; C < 2; ++C) {
                     const int col = 16 * C + ta;
-                    const double v = unit ? ((col == ucol) ? 1.0 : 0.0) : ((col < n) ? ld[8 * I + 2 * r + C] : 0.0);
+                    const double v = unit ? ((col == ucol) ? 1.0 : 0.0) : ((LEAN || col < n) ? ld[8 * I + 2 * r + C] : 0.0);
                     const double e = in ? v : 0.0;
                     Et[2 * I + C][r] = e;
                     emax = fmax(emax, fabs(e));
@@ -749,7 +785,7 @@ __device__ inline int nullspace_equalities32(const WaveCtx<32>& w, int n_eq, dou
     int* pivcol = reinterpret_cast<int*>(w.M1);                 // pivot column of each row (32 ints); M1 is idle too
     const unsigned tolbits = uniform_u32(f32_bits((float)tol));
     const int ta4 = ta << 2, rowbase4 = (lane & 48) << 2;       // byte addresses for ds_bpermute
-    bool nb0 = ta < n, nb1 = 16 + ta < n;                       // my columns are (still) non-basic
+    bool nb0 = LEAN || ta < n, nb1 = LEAN || 16 + ta < n;       // my columns are (still) non-basic
     int mypk = -1;                                              // lane k: pivot column of row k
     auto panel = [&](auto pc) {
         constexpr int p = decltype(pc)::value;
@@ -846,7 +882,7 @@ __device__ inline int nullspace_equalities32(const WaveCtx<32>& w, int n_eq, dou
 #pragma unroll
             for (int C = 0; C < 2; ++C) {
                 const int col = 16 * C + ta;
-                const bool colfree = (col < n) && !((basicmask >> col) & 1u);
+                const bool colfree = (LEAN || col < n) && !((basicmask >> col) & 1u);
                 if (colfree && pk >= 0) {
                     const int tc = __builtin_popcountll(fmask & ((1ull << col) - 1ull));
                     M2[(me + tc) * S + pk] = -Et[2 * I + C][r];
@@ -1421,9 +1457,10 @@ __device__ inline bool direction_is_independent(const WaveCtx<NP>& w, double nd2
 // set at the current x (equalities: lo - a'x, or a'(x_prev - x) for an optimality row; active inequalities: minus their
 // slack), R'y = rho by forward substitution, x += J1 y -- the minimum-H-norm correction onto the manifold.  Cold path: a few
 // instances per thousand at the default eps, none at the benchmark's.
-template <int NP, bool BOX>
-__device__ __forceinline__ double refine_on_working_set(const WaveCtx<NP>& w, double x, int iq, int Aq, double lb, double ub, double xprev) {
-    const int c = w.c, h = w.h, n = w.n;
+template <int NP, bool BOX, bool LEAN = false>
+__device__ __forceinline__ double refine_on_working_set(const WaveCtx<NP>& w, double x, int iq, int Aq, double lb, double ub, double xprev,
+                                                        const LeanRows& lr = LeanRows()) {
+    const int c = w.c, h = w.h, n = LEAN ? 32 : w.n;
     double rho = 0.0;
 #pragma unroll 1
     for (int q = 0; q < iq; ++q) {
@@ -1431,9 +1468,14 @@ __device__ __forceinline__ double refine_on_working_set(const WaveCtx<NP>& w, do
         double rq;
         if (code <= -2) {
             const int r = -2 - code;
+            if constexpr (LEAN) {   // an optimality row: a'(x_prev - x) against lo = 0
+                const double a = lean_row_elem(lr, r, w.safe_row, c);
+                rq = 0.0 + uniform_d(colsum<NP>(a * (xprev - x)));
+            } else {
             const double a = row_elem<NP>(w, r, c);
             const double xref = (uniform_i(w.rsrc[r]) >= 0) ? xprev : 0.0;
             rq = uniform_d(w.rlo[r]) + uniform_d(colsum<NP>(a * (xref - x)));
+            }
         } else if (BOX || code < 2 * n) {
             const int var = (code < n) ? code : code - n;
             rq = bcast((code < n) ? (lb - x) : (x - ub), var);
@@ -1458,18 +1500,18 @@ __device__ __forceinline__ double refine_on_working_set(const WaveCtx<NP>& w, do
     double dx = 0.0;
 #pragma unroll 1
     for (int j = 0; j < iq; ++j) dx = fma(w.M2[j * WaveCtx<NP>::S + c], bcast(y, j), dx);
-    return (c < n) ? x + dx : x;
+    return (LEAN || c < n) ? x + dx : x;
 }
 
 // BOX: the instantiation for problems whose ONLY inequalities are the bounds l <= x <= u (a plan without constraint rows: every
 // row of the table is an optimality row, i.e. an equality -- BASELINE configs 2 and 3): the candidate of a trip is a bound
 // by construction, so the row classification, the unit-row and stored-row scans, the fetch of a row normal and every
 // "bound or row?" branch of the trip are not compiled in (measured: +9 % on the headline batch)
-template <int NP, bool PROF, bool BOX>
+template <int NP, bool PROF, bool BOX, bool LEAN = false>
 __device__ int gi_inequalities(const WaveCtx<NP>& w, int nrows, double x, int iq, const int me, int Aq, double uq,
                                int iters, bool has_box, double& lb, double& ub, int max_iter, bool diag_dd, double hinv,
                                bool have_prev, double xprev, double& slack_out, double& x_out, int& iters_out, long long* prof,
-                               int hotcode, int* hot_out);
+                               int hotcode, int* hot_out, const LeanRows& lr = LeanRows());
 
 // ---------------------------------------------------------------------------------------------------------
 // Low-rank level (NP = 32):  H + eps I = D + A'WA with D diagonal and at most kLowRankMax stored rows
@@ -1489,13 +1531,13 @@ __device__ int gi_inequalities(const WaveCtx<NP>& w, int nrows, double x, int iq
 constexpr int kLowRankMax = OSOT_LOWRANK_MAX;
 // MM = compile-time bound on the rows (3 for a CoM task, else kLowRankMax): the m x m algebra is fully unrolled
 // (round 6: NP = 32 as before, and NP = 40 -- the CoM level of the reference's COMAN stacks on its own 35-coordinate robot)
-template <int NP, int MM>
+template <int NP, int MM, bool LEAN = false>
 __device__ inline void lowrank_prepare(const WaveCtx<NP>& w, const double* Ak, const double* bk, const double* wk,
                                          int m, double dcol, double cvec, bool has_c, double& x_out) {
     constexpr int S = WaveCtx<NP>::S, HV = WaveCtx<NP>::HV;
     static_assert(MM * S <= WaveCtx<NP>::M1_DOUBLES, "the rows are staged in M1");
-    const int c = w.c, h = w.h, n = w.n;
-    const bool valid = c < n;
+    const int c = w.c, h = w.h, n = LEAN ? 32 : w.n;
+    const bool valid = LEAN || c < n;
     double* M1 = w.M1;
     double* M2 = w.M2;
     double dsq, dis;   // sqrt(d_c), 1 / sqrt(d_c)
@@ -1640,14 +1682,16 @@ __device__ inline void lowrank_prepare(const WaveCtx<NP>& w, const double* Ak, c
 
 // Pre (general H):  Hc = the accumulator tiles of H + eps I (NP = 32: factor_tiles32; NP > 32: the upper triangle of tiles, factor_tiles_wide),
 // M1 is scratch.
-template <int NP, bool PROF, bool BOX = false>
+template <int NP, bool PROF, bool BOX = false, bool LEAN = false>
 __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_h,
                         double hdiag, double (&Hc)[NP / WaveCtx<NP>::HV], bool has_box, double& lb, double& ub, int max_iter,
                         bool have_prev, double xprev, double& x_out, int& iters_out, long long* prof,
                         double& slack_out, bool prepared = false, double xprep = 0.0, int hotcode = -1, int* hot_out = nullptr,
-                        int dense_rank_in = -1, int dense_neq_in = 0, double dense_x_in = 0.0, double dense_hinv_in = 0.0) {
+                        int dense_rank_in = -1, int dense_neq_in = 0, double dense_x_in = 0.0, double dense_hinv_in = 0.0,
+                        const LeanRows& lr = LeanRows()) {
+    static_assert(!LEAN || (NP == 32 && BOX), "the lean path is a path of the 32-lane BOX instantiation");
     constexpr int HV = WaveCtx<NP>::HV, S = WaveCtx<NP>::S;
-    const int n = w_in.n;
+    const int n = LEAN ? 32 : w_in.n;
     double* M1 = w_in.M1;
     double* M2 = w_in.M2;
     double* V0 = w_in.V;
@@ -1666,9 +1710,10 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
     {   // ---------------- factorisation phase (own scope: see the launder_i note below) ----------------
     WaveCtx<NP> w1 = w_in;
     { const int l1 = launder_i(WaveCtx<NP>::lane_of(w_in.c, w_in.h)); w1.c = WaveCtx<NP>::col_of(l1); w1.h = WaveCtx<NP>::half_of(l1); }
+    if constexpr (LEAN) w1.n = 32;
     const WaveCtx<NP>& w = w1;
     const int c = w.c, h = w.h;
-    const bool valid = c < n;
+    const bool valid = LEAN || c < n;
 
     if (dense_ns) {
         // (nothing to factorise: J2' is in M2, x is the equality-constrained minimiser)
@@ -1692,7 +1737,7 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
         int stf;
         if constexpr (NP > 32) {
             stf = factor_tiles_wide<NP, wide_tiles(NP)>(w, Hc, g, x);
-        } else stf = factor_tiles32(w, Hc, g, x);
+        } else stf = factor_tiles32<false, false, LEAN>(w, Hc, g, x);
         stf = uniform_i(stf);
         if (stf != QP_SOLVED) { x_out = 0.0; iters_out = 0; return stf; }
         OSOT_PH_END(PH_CHOL);
@@ -1705,9 +1750,10 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
     // (the lane coordinates are re-derived here so that nothing computed for the factorisation stays live)
     WaveCtx<NP> w2 = w_in;
     { const int l2 = launder_i(WaveCtx<NP>::lane_of(w_in.c, w_in.h)); w2.c = WaveCtx<NP>::col_of(l2); w2.h = WaveCtx<NP>::half_of(l2); }
+    if constexpr (LEAN) w2.n = 32;
     const WaveCtx<NP>& w = w2;
     const int c = w.c, h = w.h;
-    const bool valid = c < n;
+    const bool valid = LEAN || c < n;
     int iq = 0;          // size of the working set (wave-uniform)
     int Aq = -1;         // lane q < iq: code of the constraint at working-set position q
     double uq = 0.0;     // lane q < iq: its multiplier (inequalities only)
@@ -1716,9 +1762,9 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
     // ---- equalities first --------------------------------------------------------------------------
     // classify all rows in parallel (lane = row), then walk the equality rows with the next row's
     // elements already in flight (one HBM/L2 round trip per row would otherwise sit on the critical path)
-    int n_eq = 0;
+    int n_eq = LEAN ? nrows : 0;   // (LEAN: every row of the implicit table is an equality, and the list is the table)
     bool local_eq = false;   // an equality among the level's task-local rows: x_prev does not satisfy it
-    for (int r0 = 0; r0 < (dense_ns ? 0 : nrows); r0 += 64) {
+    for (int r0 = 0; r0 < ((dense_ns || LEAN) ? 0 : nrows); r0 += 64) {
         const int r = r0 + WaveCtx<NP>::lane_of(c, h);
         bool is_eq = false, is_loc = false;
         if (r < nrows) {
@@ -1732,7 +1778,7 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
         if (is_eq) w.eqlist[n_eq + lanes_below(mask)] = r;
         n_eq += __builtin_popcountll(mask);
     }
-    wave_sync();
+    if constexpr (!LEAN) wave_sync();
     // many equalities under a diagonal Hessian, ALL satisfied by the previous level's solution (optimality rows and
     // global equality rows are; a task-local equality of this level is not: then the generic path runs): null-space
     // elimination instead of n_eq Householder updates of the full J (see nullspace_equalities32)
@@ -1750,7 +1796,7 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
         iq = dense_rank; iters += dense_neq; used_nullspace = true;
     }
     if (NP == 32 && diag_h && have_prev && !local_eq && n_eq >= 8 && n_eq <= 32 && n - n_eq <= kNullMax) {
-        const int r_ns = uniform_i(nullspace_equalities32<PROF>(reinterpret_cast<const WaveCtx<32>&>(w), n_eq, hdiag, g, xprev, x, prof));
+        const int r_ns = uniform_i(nullspace_equalities32<PROF, LEAN>(reinterpret_cast<const WaveCtx<32>&>(w), n_eq, hdiag, g, xprev, x, prof, lr));
         if (r_ns >= 0) { iq = r_ns; iters += n_eq; used_nullspace = true; n_eq = 0; }
     }
     if constexpr (NP == 40) {     // round 6: the 40-lane layout (the reference's 35-coordinate COMAN) takes the same route
@@ -1777,16 +1823,19 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
     double* V3p = w.V + 3 * WaveCtx<NP>::LW;
     double rq[4];    // rows e .. e+3 of the list at my column, requested ahead of their use
 #pragma unroll
-    for (int i = 0; i < 4; ++i) rq[i] = (i < n_eq) ? row_elem<NP>(w, uniform_i(w.eqlist[i]), c) : 0.0;
+    for (int i = 0; i < 4; ++i) {
+        if constexpr (LEAN) rq[i] = (i < n_eq) ? lean_row_elem(lr, i, w.safe_row, c) : 0.0;
+        else rq[i] = (i < n_eq) ? row_elem<NP>(w, uniform_i(w.eqlist[i]), c) : 0.0;
+    }
     for (int e = 0; e < n_eq;) {
         // (the 64-lane layouts only: at NP = 32 -- two wavefronts per SIMD, three such rows at config 3 -- the pair's code and registers
         //  cost more than its passes save: measured -1.4 % on the headline batch with pairs on)
         const bool have_b = (NP > 32) && e + 1 < n_eq;
-        const int r = uniform_i(w.eqlist[e]);
-        const int rb = uniform_i(w.eqlist[have_b ? e + 1 : e]);
+        const int r = LEAN ? e : uniform_i(w.eqlist[e]);
+        const int rb = LEAN ? e : uniform_i(w.eqlist[have_b ? e + 1 : e]);
         const double a = rq[0], b = have_b ? rq[1] : 0.0;
-        const double lo = uniform_d(w.rlo[r]), lob = uniform_d(w.rlo[rb]);
-        const int src = uniform_i(w.rsrc[r]), srcb = uniform_i(w.rsrc[rb]);
+        const double lo = LEAN ? 0.0 : uniform_d(w.rlo[r]), lob = LEAN ? 0.0 : uniform_d(w.rlo[rb]);
+        const int src = LEAN ? 0 : uniform_i(w.rsrc[r]), srcb = LEAN ? 0 : uniform_i(w.rsrc[rb]);   // (LEAN: optimality rows all)
         // right-hand side relative to x: lo - a'x, or a'(x_prev - x) for an optimality row (x_prev, the solution of the
         // last level solved, satisfies a'x_prev = a'x_j for the rows of every level j above it)
         const double xref = (src >= 0) ? xprev : 0.0, xrefb = (srcb >= 0) ? xprev : 0.0;
@@ -1888,9 +1937,12 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
             }
         }
         // the rows ahead: shift the queue by what was consumed and request the missing ones
-        if (adv == 1) {
+        // (rows go in pairs -- adv == 2 -- in the 64-lane layouts only; LEAN is NP = 32, see the static_assert above: the pair arm,
+        //  which reads the list the lean path never fills, is not compiled into it)
+        if (LEAN || adv == 1) {
             rq[0] = rq[1]; rq[1] = rq[2]; rq[2] = rq[3];
-            rq[3] = (e + 4 < n_eq) ? row_elem<NP>(w, uniform_i(w.eqlist[e + 4]), c) : 0.0;
+            if constexpr (LEAN) rq[3] = (e + 4 < n_eq) ? lean_row_elem(lr, e + 4, w.safe_row, c) : 0.0;
+            else rq[3] = (e + 4 < n_eq) ? row_elem<NP>(w, uniform_i(w.eqlist[e + 4]), c) : 0.0;
         } else {
             rq[0] = rq[2]; rq[1] = rq[3];
             rq[2] = (e + 4 < n_eq) ? row_elem<NP>(w, uniform_i(w.eqlist[e + 4]), c) : 0.0;
@@ -1905,21 +1957,23 @@ __device__ int gi_solve(const WaveCtx<NP>& w_in, int nrows, double g, bool diag_
     // ---- inequality loop -----------------------------------------------------------------------------
     WaveCtx<NP> w3 = w_in;
     { const int l3 = launder_i(WaveCtx<NP>::lane_of(w_in.c, w_in.h)); w3.c = WaveCtx<NP>::col_of(l3); w3.h = WaveCtx<NP>::half_of(l3); }
+    if constexpr (LEAN) w3.n = 32;
     // after the null-space path the equality rows of J are zero, so |J'n|^2 no longer measures n'H^-1 n;
     // the diagonal of H^-1 does (hinv > 0 selects that in the dependency test)
     const double hinv = dense_ns ? dense_hinv : ((used_nullspace && valid) ? fast_rcp(hdiag) : 0.0);
-    return gi_inequalities<NP, PROF, BOX>(w3, nrows, x, iq, me, Aq, uq, iters, has_box, lb, ub, max_iter, used_nullspace, hinv,
-                                     have_prev, xprev, slack_out, x_out, iters_out, prof, hotcode, hot_out);
+    return gi_inequalities<NP, PROF, BOX, LEAN>(w3, nrows, x, iq, me, Aq, uq, iters, has_box, lb, ub, max_iter, used_nullspace, hinv,
+                                     have_prev, xprev, slack_out, x_out, iters_out, prof, hotcode, hot_out, lr);
 }
 
-template <int NP, bool PROF, bool BOX>
+template <int NP, bool PROF, bool BOX, bool LEAN>
 __device__ int gi_inequalities(const WaveCtx<NP>& w, int nrows, double x, int iq, const int me, int Aq, double uq,
                                int iters, bool has_box, double& lb, double& ub, int max_iter, bool diag_dd, double hinv,
                                bool have_prev, double xprev, double& slack_out, double& x_out, int& iters_out, long long* prof,
-                               int hotcode, int* hot_out) {
+                               int hotcode, int* hot_out, const LeanRows& lr) {
+    static_assert(!LEAN || (NP == 32 && BOX), "the lean path is a path of the 32-lane BOX instantiation");
     constexpr int S = WaveCtx<NP>::S;
-    const int c = w.c, h = w.h, n = w.n;
-    const bool valid = c < n;
+    const int c = w.c, h = w.h, n = LEAN ? 32 : w.n;
+    const bool valid = LEAN || c < n;
     double* M1 = w.M1;
     double* M2 = w.M2;
     double* V0 = w.V;
@@ -2351,7 +2405,7 @@ __device__ int gi_inequalities(const WaveCtx<NP>& w, int nrows, double x, int iq
                 }
                 if (!diag_dd && refine_left > 0 && -s_ip <= kSlackTol * fmax(1.0, bmag0)) {
                     refine_left--;
-                    x = refine_on_working_set<NP, BOX>(w, x, iq, Aq, lb, ub, xprev);
+                    x = refine_on_working_set<NP, BOX, LEAN>(w, x, iq, Aq, lb, ub, xprev, lr);
                     degenerate_done = true; break;
                 }
             }
@@ -2366,7 +2420,7 @@ __device__ int gi_inequalities(const WaveCtx<NP>& w, int nrows, double x, int iq
                     if (!diag_dd && refine_left > 0 && -s_ip > kRefineFloor * fmax(1.0, bmag)) {
                         // round-off of the iterate, not of the problem: put x back onto the working set and scan again
                         refine_left--;
-                        x = refine_on_working_set<NP, BOX>(w, x, iq, Aq, lb, ub, xprev);
+                        x = refine_on_working_set<NP, BOX, LEAN>(w, x, iq, Aq, lb, ub, xprev, lr);
                         degenerate_done = true; break;
                     }
                     // accepted as satisfied: the LOWER levels must accept the same point (their optimality rows pin x
