@@ -648,6 +648,8 @@ int osot_qp_solve_batch_admm_warm(int B, int n, int nc, const double* H, const d
 #define OSOT_KIN_MAX_FRAMES 8
 #define OSOT_KIN_MAX_PAIRS 32
 #define OSOT_KIN_MAX_POINTS 16
+#define OSOT_KIN_MAX_HULL_VERTICES 256
+#define OSOT_KIN_MAX_HULL 32                 /* vertices of ONE hull */
 enum { OSOT_JOINT_REVOLUTE = 0, OSOT_JOINT_PRISMATIC = 1 };
 typedef struct {
     int n;                                   /* joints = generalised coordinates; tree order: parent[j] < j     */
@@ -690,7 +692,8 @@ typedef struct {
      *     pair_radius[p][1] is a rounding radius (0 for a sharp box).
      * Distance = exact closest points of side a's axis segment and the box (piecewise-quadratic minimisation over the
      * segment parameter); a segment that touches or enters the box has no normal: distance -r_a - r_b, zero row (the
-     * reference caps the bound at 0 there, CollisionAvoidance.cpp:141-146).  Box against box is not offered.
+     * reference caps the bound at 0 there, CollisionAvoidance.cpp:141-146).  Box against box and every other pair of convex
+     * shapes: the CONVEX SHAPES block below.
      * All zero (the value of a struct written before these fields existed) = capsule pairs on links only. */
     int pair_kind[OSOT_KIN_MAX_PAIRS];
     int pair_env[OSOT_KIN_MAX_PAIRS];
@@ -708,6 +711,28 @@ typedef struct {
      *           joints both chains share drop out exactly, the joints of the base's own chain enter with a minus sign.
      * With frame_body[f] the rotation is R_d' instead (Ad(bR_d') after the R_b' of the relative Jacobian, Cartesian.cpp:93-100). */
     int frame_base[OSOT_KIN_MAX_FRAMES];
+    /* CONVEX SHAPES on both sides of a pair (what CollisionAvoidance.cpp:96-200 takes from the URDF: boxes, cylinders, spheres
+     * and meshes).  A shape is a convex CORE grown by the rounding radius pair_radius[p][side] >= 0:
+     *   OSOT_SHAPE_CAPSULE  the segment pair_seg[p][side] (carrier frame); zero length = a sphere
+     *   OSOT_SHAPE_BOX      size = half extents
+     *   OSOT_SHAPE_CYLINDER size = (radius, unused, half length), axis = z of the shape frame
+     *   OSOT_SHAPE_HULL     the convex hull of 1 .. 32 vertices hull_vertex[first .. first + count - 1] (shape frame): a convex
+     *                       mesh.  Non-convex meshes are not offered.
+     * SIDE A: pair_kind_a[p] (0 = the capsule of pair_seg[p][0], as before), pair_size_a, and link_T_shape =
+     * (pair_shape_R_a[p], pair_shape_p_a[p]) in the frame of pair_joint[p][0]'s link.  SIDE B keeps pair_kind / pair_box (its size) /
+     * pair_shape_R / pair_shape_p and its carriers (link, world, environment pose).  pair_hull[p][side] = {first vertex, count}.
+     * A pair of capsule / capsule or capsule / box keeps its closed form, bit for bit.  Every other pair runs GJK on the two cores
+     * in double precision (opensot_amd/csrc/osot_convex.h): distance = |ca - cb| - r_a - r_b with the witnesses ca, cb on the
+     * cores; intersecting cores have no normal: distance -r_a - r_b, zero row, as for the segment inside a box above.  Such a
+     * model is served by osot_kinematics; osot_control_cycle / osot_control_rollout refuse it when pair outputs are bound.
+     * All zero = no convex pair.  (The block sits in front of the contact points, which stay the struct's last members.) */
+    int pair_kind_a[OSOT_KIN_MAX_PAIRS];
+    double pair_size_a[OSOT_KIN_MAX_PAIRS][3];
+    double pair_shape_R_a[OSOT_KIN_MAX_PAIRS][9];
+    double pair_shape_p_a[OSOT_KIN_MAX_PAIRS][3];
+    int pair_hull[OSOT_KIN_MAX_PAIRS][2][2];
+    int n_hull_vertices;                         /* 0 .. OSOT_KIN_MAX_HULL_VERTICES                                   */
+    double hull_vertex[OSOT_KIN_MAX_HULL_VERTICES][3];
     /* CONTACT POINTS (velocity::ConvexHull: convex_hull::getSupportPolygonPoints asks the model for getPose(link).translation() of
      * every link in contact, src/utils/convex_hull_utils.cpp:142-174): point i is fixed at point_p[i] in the frame of joint
      * point_joint[i]'s link; the producer writes its world position to osot_kin_batch.points.  All zero = none. */
@@ -715,7 +740,7 @@ typedef struct {
     int point_joint[OSOT_KIN_MAX_POINTS];        /* 0 .. n - 1                                                        */
     double point_p[OSOT_KIN_MAX_POINTS][3];
 } osot_kin_desc;
-enum { OSOT_SHAPE_CAPSULE = 0, OSOT_SHAPE_BOX = 1 };
+enum { OSOT_SHAPE_CAPSULE = 0, OSOT_SHAPE_BOX = 1, OSOT_SHAPE_CYLINDER = 2, OSOT_SHAPE_HULL = 3 };
 #define OSOT_KIN_MAX_ENV 16
 typedef struct {
     int B;
@@ -733,6 +758,10 @@ typedef struct {
     const double* env_pose;                        /* [n_env][12] world_T_shape = [R row-major | p] of the environment
                                                       shapes (moveCollisionShape), or NULL when n_env = 0           */
     long long env_pose_stride;                     /* 0: one world shared by all instances; 12 n_env: per instance  */
+    double* pair_points;                           /* [B][n_pairs][6] the witness points of every pair, ca then cb, in the
+                                                      world and ON THE CORES (the capsule axis, the box, the hull: not the
+                                                      rounded surface) -- what the reference's collision module returns next to
+                                                      the distance; or NULL                                          */
     double* points;                                /* [B][n_points][3] world positions of the contact points (the
                                                       OSOT_ROWS_CONVEX_HULL leaf p2), or NULL                        */
 } osot_kin_batch;
@@ -740,6 +769,20 @@ typedef struct osot_kin osot_kin;
 int osot_kin_create(const osot_kin_desc* desc, int device, osot_kin** out);
 int osot_kin_destroy(osot_kin* k);
 int osot_kinematics(osot_kin* k, const osot_kin_batch* batch, void* hip_stream);
+/* Distance of two convex shapes ON THE HOST (no device is touched): the code the producer's lanes run, for a setup-time check
+ * ("do my shapes overlap at q0?").  size as in the CONVEX SHAPES block above; a capsule: size[2] = half length along z of the shape frame;
+ * world_T_a / world_T_b: [R row-major | p], 12 doubles.  Always GJK, also for the pairs the producer has a closed form for.
+ * dist = |ca - cb| - r_a - r_b; ca, cb [3] on the cores (equal when the cores intersect); iterations: support evaluations.
+ * dist, ca, cb, iterations may each be NULL. */
+typedef struct {
+    int kind;                    /* OSOT_SHAPE_*                                                                       */
+    double size[3];
+    double radius;               /* rounding radius >= 0                                                               */
+    int n_vertices;              /* OSOT_SHAPE_HULL: 1 .. OSOT_KIN_MAX_HULL                                             */
+    const double* vertices;      /* [n_vertices][3] in the shape frame                                                 */
+} osot_shape;
+int osot_shape_distance(const osot_shape* a, const double* world_T_a, const osot_shape* b, const double* world_T_b, double* dist,
+                        double* ca, double* cb, int* iterations);
 
 /* The body of the reference's control loop for B robots in ONE launch (examples/cpp/coman_ik.cpp:186-219:
  * `model.update(); stack->update(); solver->solve(dq); q = model.sum(q, dq)`): per instance the same wavefront runs

@@ -124,7 +124,8 @@ class IdModel(C.Structure):
 KIN_MAX_JOINTS, KIN_MAX_FRAMES, KIN_MAX_PAIRS = 64, 8, 32
 KIN_MAX_ENV = 16
 KIN_MAX_POINTS = 16
-SHAPE_CAPSULE, SHAPE_BOX = 0, 1
+KIN_MAX_HULL_VERTICES, KIN_MAX_HULL = 256, 32      # hull vertices of a model / of one hull
+SHAPE_CAPSULE, SHAPE_BOX, SHAPE_CYLINDER, SHAPE_HULL = 0, 1, 2, 3
 JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
 
 
@@ -143,6 +144,10 @@ class KinDesc(C.Structure):
                 ("pair_box", (C.c_double * 3) * KIN_MAX_PAIRS), ("pair_shape_R", (C.c_double * 9) * KIN_MAX_PAIRS),
                 ("pair_shape_p", (C.c_double * 3) * KIN_MAX_PAIRS), ("n_env", C.c_int),
                 ("frame_base", C.c_int * KIN_MAX_FRAMES),
+                ("pair_kind_a", C.c_int * KIN_MAX_PAIRS), ("pair_size_a", (C.c_double * 3) * KIN_MAX_PAIRS),
+                ("pair_shape_R_a", (C.c_double * 9) * KIN_MAX_PAIRS), ("pair_shape_p_a", (C.c_double * 3) * KIN_MAX_PAIRS),
+                ("pair_hull", ((C.c_int * 2) * 2) * KIN_MAX_PAIRS), ("n_hull_vertices", C.c_int),
+                ("hull_vertex", (C.c_double * 3) * KIN_MAX_HULL_VERTICES),
                 ("n_points", C.c_int), ("point_joint", C.c_int * KIN_MAX_POINTS), ("point_p", (C.c_double * 3) * KIN_MAX_POINTS)]
 
 
@@ -151,7 +156,12 @@ class KinBatch(C.Structure):
                 ("frame_J", C.c_void_p * KIN_MAX_FRAMES), ("frame_J_stride", C.c_longlong * KIN_MAX_FRAMES),
                 ("com", C.c_void_p), ("com_J", C.c_void_p), ("com_J_stride", C.c_longlong),
                 ("pair_dist", C.c_void_p), ("pair_J", C.c_void_p), ("pair_J_stride", C.c_longlong),
-                ("env_pose", C.c_void_p), ("env_pose_stride", C.c_longlong), ("points", C.c_void_p)]
+                ("env_pose", C.c_void_p), ("env_pose_stride", C.c_longlong), ("pair_points", C.c_void_p),
+                ("points", C.c_void_p)]
+
+
+class Shape(C.Structure):
+    _fields_ = [("kind", C.c_int), ("size", C.c_double * 3), ("radius", C.c_double), ("n_vertices", C.c_int), ("vertices", dp)]
 
 
 class DynDesc(C.Structure):
@@ -193,7 +203,7 @@ SYMBOLS = [
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
-    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
+    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
     "osot_grad_create", "osot_grad_destroy", "osot_posture_gradient", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
     "osot_backend_create", "osot_backend_destroy", "osot_backend_init_problem",
     "osot_backend_update_task", "osot_backend_update_constraints", "osot_backend_update_bounds",
@@ -212,7 +222,7 @@ STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound
            "osot_plan_desc": PlanDesc, "osot_qp_batch": QpBatch, "osot_leaf_ptrs": LeafPtrs, "osot_leaf_batch": LeafBatch,
            "osot_assembled_out": AssembledOut, "osot_backend_options": BackendOptions, "osot_nhqp_options": NhqpOptions,
            "osot_admm_options": AdmmOptions, "osot_id_model": IdModel, "osot_kin_desc": KinDesc, "osot_kin_batch": KinBatch,
-           "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch}
+           "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch, "osot_shape": Shape}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -271,6 +281,7 @@ def lib():
     L.osot_kin_create.argtypes = [C.POINTER(KinDesc), C.c_int, C.POINTER(vp)]
     L.osot_kin_destroy.argtypes = [vp]
     L.osot_kinematics.argtypes = [vp, C.POINTER(KinBatch), vp]
+    L.osot_shape_distance.argtypes = [C.POINTER(Shape), dp, C.POINTER(Shape), dp, dp, dp, dp, ip]
     L.osot_dyn_create.argtypes = [C.POINTER(KinDesc), C.POINTER(DynDesc), C.c_int, C.POINTER(vp)]
     L.osot_dyn_destroy.argtypes = [vp]
     L.osot_dynamics.argtypes = [vp, C.POINTER(DynBatch), vp]

@@ -15,10 +15,13 @@
 //      (world frame) -> distance d = |c_a - c_b| - r_a - r_b and unit normal n -> LDS; then one coalesced row per
 //      pair, lane j = joint: J_d[j] = n . (v_j(c_a) [j moves a] - v_j(c_b) [j moves b]),  v_j(c) = z_j x (c - p_j)
 //      (revolute) or z_j (prismatic).  (A point of the capsule SURFACE, c - r n, has the same velocity along n.)
+//      CONVEX instantiation: a pair that is not capsule / capsule or capsule / box (box, cylinder or hull on either side) gets its
+//      closest points from the lane's own GJK run (osot_convex.h); the table and the row loop behind it are the same.
 // HBM-bound by construction: reads 8 n bytes of q, writes (6 F + 3) n 8 + 96 F + 24 bytes per instance.
 #pragma once
 #include <osot_team.h>
 #include <osot_mi355x.h>
+#include <osot_convex.h>
 
 namespace osot {
 
@@ -194,6 +197,41 @@ __device__ inline __attribute__((noinline)) void kin_points(const DevKin* __rest
 #pragma unroll
     for (int i = 0; i < 3; ++i) points[(inst * np + j) * 3 + i] = wp[i] + Tw[jp * TS + 9 + i];
 }
+// the witness points of a pair, ca then cb (lane = pair), from the pair table in LDS -> pair_points [B][n_pairs][6].  Not inlined, like
+// kin_points: the instantiations keep their register allocation.
+__device__ inline __attribute__((noinline)) void kin_pair_points(double* out, const long long row, const double* pw) {
+#pragma unroll
+    for (int i = 0; i < 6; ++i) out[row * 6 + i] = pw[3 + i];
+}
+// Closest points of a CONVEX pair (lane = pair): the two cores from the model and the carrier frames (side a: its link; side b: link,
+// world or environment pose), GJK, the witnesses.  e: the world end points of the two capsule segments (a side that is a capsule).
+// Not inlined: one body for both sizes of the producer, and the closed-form pairs beside it keep their code.
+__device__ inline __attribute__((noinline)) void kin_convex_pair(const DevKin* __restrict__ K, const int p, const double* Ra, const double* pa,
+                                                                 const double* Rc, const double* pc, const double* e, double* ca, double* cb) {
+    ConvexCore C[2];
+#pragma unroll
+    for (int sd = 0; sd < 2; ++sd) {
+        const int kind = sd == 0 ? K->d.pair_kind_a[p] : K->d.pair_kind[p];
+        if (kind == OSOT_SHAPE_CAPSULE) { convex_segment(C[sd], e + 6 * sd, e + 6 * sd + 3); continue; }
+        const double* Rl = sd == 0 ? Ra : Rc;
+        const double* pl = sd == 0 ? pa : pc;
+        const double* SR = sd == 0 ? K->d.pair_shape_R_a[p] : K->d.pair_shape_R[p];
+        const double* Sp = sd == 0 ? K->d.pair_shape_p_a[p] : K->d.pair_shape_p[p];
+        const double* sz = sd == 0 ? K->d.pair_size_a[p] : K->d.pair_box[p];
+        double t[3];
+        mat3_mul(Rl, SR, C[sd].R);
+        mat3_vec(Rl, Sp, t);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { C[sd].p[i] = pl[i] + t[i]; C[sd].s[i] = sz[i]; }
+        C[sd].kind = kind;
+        C[sd].v = &K->d.hull_vertex[K->d.pair_hull[p][sd][0]][0];
+        C[sd].nv = K->d.pair_hull[p][sd][1];
+    }
+    GjkResult r;
+    gjk_closest(C[0], C[1], r);
+#pragma unroll
+    for (int i = 0; i < 3; ++i) { ca[i] = r.ca[i]; cb[i] = r.cb[i]; }
+}
 // LDS one instance of kin_instance needs, in doubles (the int / 64-bit tables included): transforms, axes, centres of mass, parents,
 // ancestor masks -- and the pair table of the PAIRS instantiation
 template <int JMAX> constexpr int kin_lds_doubles(bool pairs) {
@@ -203,13 +241,14 @@ template <int JMAX> constexpr int kin_lds_doubles(bool pairs) {
 // colsum<JMAX>).  `lds` = kin_lds_doubles<JMAX>(PAIRS) doubles of this instance's own.  The kernel below calls it for one instance
 // per wavefront (JMAX = 64) or two (JMAX = 32: the halves); osot_control_cycle_kernel calls it in front of the instance's update.
 // PAIRS: the instantiation with the self-collision stage (step 5); the other one keeps the leaner register / LDS budget
+// CONVEX (with PAIRS): the stage also serves pairs of convex shapes (kin_convex_pair); launched only for a model that has one
 // developer knob (tools/build_variant.sh NAME -DOSOT_KIN_PHASES): instance 0 prints the clock count of every stage
 #ifdef OSOT_KIN_PHASES
 #define KIN_PHASE(tag) do { const long long t_ = (long long)clock64(); if (inst == 0 && j == 0) printf("KIN " tag " %lld\n", t_ - kph_); kph_ = (long long)clock64(); } while (0)
 #else
 #define KIN_PHASE(tag) do { } while (0)
 #endif
-template <bool PAIRS, int JMAX>
+template <bool PAIRS, int JMAX, bool CONVEX = false>
 __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const osot_kin_batch& Bt, const long long inst, const bool live,
                                              const int j, double* lds) {
     constexpr int TS = OSOT_KIN_TS;
@@ -513,10 +552,12 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
     // ---- 5. self-collision pairs
     if constexpr (PAIRS) {
     const int np = K->d.n_pairs;
-    if (np > 0 && (Bt.pair_dist || Bt.pair_J)) {
+    if (np > 0 && (Bt.pair_dist || Bt.pair_J || Bt.pair_points)) {
         if (j < np && live) {
             double e[2][6];
             double Rc[9], pc[3];      // carrier frame of side b (link, world, or the runtime pose of an environment shape)
+            double Ra[9], pa[3];      // CONVEX: ... and of side a (its link)
+            (void)Ra; (void)pa;
 #pragma unroll
             for (int sd = 0; sd < 2; ++sd) {
                 const int js = K->d.pair_joint[j][sd];
@@ -550,9 +591,24 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
 #pragma unroll
                     for (int i = 0; i < 3; ++i) pc[i] = pj[i];
                 }
+                if constexpr (CONVEX) {
+                    if (sd == 0) {
+#pragma unroll
+                        for (int i = 0; i < 9; ++i) Ra[i] = Rj[i];
+#pragma unroll
+                        for (int i = 0; i < 3; ++i) pa[i] = pj[i];
+                    }
+                }
             }
             double ca[3], cb[3];
-            if (K->d.pair_kind[j] == OSOT_SHAPE_BOX) {
+            bool closed_form = true;      // capsule / capsule and capsule / box: the same code, the same bits, in every instantiation
+            if constexpr (CONVEX) {
+                const int ka = K->d.pair_kind_a[j], kb = K->d.pair_kind[j];
+                closed_form = ka == OSOT_SHAPE_CAPSULE && (kb == OSOT_SHAPE_CAPSULE || kb == OSOT_SHAPE_BOX);
+                if (!closed_form) kin_convex_pair(K, j, Ra, pa, Rc, pc, &e[0][0], ca, cb);
+            }
+            if (!closed_form) {      // (ca, cb are there)
+            } else if (K->d.pair_kind[j] == OSOT_SHAPE_BOX) {
                 // box frame in the world: (Rc, pc) o (shape_R, shape_p); side a's segment goes into it, the closest points
                 // come back out
                 double Rb[9], tb[3], pb[3];
@@ -582,6 +638,7 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
 #pragma unroll
             for (int i = 0; i < 3; ++i) { Pw[j * 9 + i] = dv[i] * il; Pw[j * 9 + 3 + i] = ca[i]; Pw[j * 9 + 6 + i] = cb[i]; }
             if (Bt.pair_dist) Bt.pair_dist[inst * np + j] = len - K->d.pair_radius[j][0] - K->d.pair_radius[j][1];
+            if (Bt.pair_points) kin_pair_points(Bt.pair_points, inst * np + j, Pw + j * 9);
         }
         wave_sync();
         if (Bt.pair_J) {
@@ -612,7 +669,7 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
 
 // JMAX = 32: TWO instances per wavefront (lanes 0..31 and 32..63 each run a robot of <= 32 joints: every instruction, every
 // 64-lane store carries two instances);  JMAX = 64: one instance per wavefront.
-template <bool PAIRS, int JMAX>
+template <bool PAIRS, int JMAX, bool CONVEX = false>
 __global__ void __launch_bounds__(64) osot_kin_kernel(const DevKin* __restrict__ K, const osot_kin_batch Bt) {
     constexpr int PACK = 64 / JMAX;
     constexpr int SLICE = kin_lds_doubles<JMAX>(PAIRS);
@@ -621,7 +678,7 @@ __global__ void __launch_bounds__(64) osot_kin_kernel(const DevKin* __restrict__
     const int j = (PACK == 2) ? (int)(threadIdx.x & 31u) : (int)threadIdx.x;
     const long long inst = (long long)blockIdx.x * PACK + sub;
     const bool live = inst < Bt.B;            // (an odd batch leaves the last wavefront's second half idle)
-    kin_instance<PAIRS, JMAX>(K, Bt, inst, live, j, kin_lds + sub * SLICE);
+    kin_instance<PAIRS, JMAX, CONVEX>(K, Bt, inst, live, j, kin_lds + sub * SLICE);
 }
 
 }  // namespace osot

@@ -200,9 +200,12 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
         OSOT_F(n_frames) OSOT_F(frame_joint) OSOT_F(frame_R) OSOT_F(frame_p) OSOT_F(n_pairs) OSOT_F(pair_joint) OSOT_F(pair_seg)
         OSOT_F(pair_radius) OSOT_F(frame_body) OSOT_F(frame_col_mask) OSOT_F(com_col_mask) OSOT_F(pair_kind) OSOT_F(pair_env)
         OSOT_F(pair_box) OSOT_F(pair_shape_R) OSOT_F(pair_shape_p) OSOT_F(n_env) OSOT_F(frame_base)
-        OSOT_F(n_points) OSOT_F(point_joint) OSOT_F(point_p) OSOT_LAYOUT_END()
+        OSOT_F(pair_kind_a) OSOT_F(pair_size_a) OSOT_F(pair_shape_R_a) OSOT_F(pair_shape_p_a) OSOT_F(pair_hull) OSOT_F(n_hull_vertices)
+        OSOT_F(hull_vertex) OSOT_F(n_points) OSOT_F(point_joint) OSOT_F(point_p) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_kin_batch) OSOT_F(B) OSOT_F(q) OSOT_F(frame_pose) OSOT_F(frame_J) OSOT_F(frame_J_stride) OSOT_F(com)
-        OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(pair_dist) OSOT_F(pair_J) OSOT_F(pair_J_stride) OSOT_F(env_pose) OSOT_F(env_pose_stride) OSOT_F(points) OSOT_LAYOUT_END()
+        OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(pair_dist) OSOT_F(pair_J) OSOT_F(pair_J_stride) OSOT_F(env_pose) OSOT_F(env_pose_stride)
+        OSOT_F(pair_points) OSOT_F(points) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_shape) OSOT_F(kind) OSOT_F(size) OSOT_F(radius) OSOT_F(n_vertices) OSOT_F(vertices) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_desc) OSOT_F(inertia) OSOT_F(gravity) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_batch) OSOT_F(B) OSOT_F(q) OSOT_F(qdot) OSOT_F(M) OSOT_F(M_stride) OSOT_F(h) OSOT_F(frame_Jdot_qdot)
         OSOT_F(frame_Jdot_qdot_stride) OSOT_F(com_Jdot_qdot) OSOT_F(com_Jdot_qdot_stride) OSOT_F(cmm_lin) OSOT_F(cmm_lin_stride)
@@ -747,7 +750,7 @@ static int ihqp_launch(osot_solver* s, const osot_qp_batch* b, void* hip_stream,
     LaunchFacts facts;
     facts.T = T; facts.nc = P.nc; facts.fused = fused != nullptr; facts.control = control != nullptr; facts.prof = prof != nullptr;
     facts.roll = control && (control->steps > 1 || control->dq_steps || control->status_steps);
-    facts.pairs_out = control && control->K_pairs > 0 && (control->Bt.pair_dist || control->Bt.pair_J);
+    facts.pairs_out = control && control->K_pairs > 0 && (control->Bt.pair_dist || control->Bt.pair_J || control->Bt.pair_points);
     facts.plan_extra = s->any_inactive || (pl.has_regularisation && pl.regularisation_dense);
     for (int k = 0; k < pl.n_levels; ++k) facts.plan_extra = facts.plan_extra || (s->h_uplan.dense_level[k] != 0);
     facts.hotstart = s->hotstart != 0; facts.force_extra = force && force[0] == '1'; facts.specialise = s->specialise != 0;
@@ -1137,7 +1140,25 @@ int osot_backend_get_num_constraints(osot_backend* be, int* nc) {
 struct osot_kin {
     DevKin* dev;
     int n, n_frames, n_pairs, n_env, device;
+    int n_convex;      // pairs that are not capsule / capsule or capsule / box: served by the CONVEX instantiation of the producer alone
 };
+
+namespace {
+// a pair of the closed forms (osot_kin.h, stage 5)?
+bool pair_is_closed_form(const osot_kin_desc* d, int p) {
+    return d->pair_kind_a[p] == OSOT_SHAPE_CAPSULE && (d->pair_kind[p] == OSOT_SHAPE_CAPSULE || d->pair_kind[p] == OSOT_SHAPE_BOX);
+}
+// one side of a pair beyond the capsule: sizes, link_T_shape, the hull's vertex range
+int check_pair_shape(const osot_kin_desc* d, int kind, const double* size, double radius, const double* R, const int* hull, const char** why) {
+    if ((*why = convex_check_size(kind, size, radius)) != nullptr) return OSOT_ERR_INVALID;
+    if ((*why = convex_check_rotation(R)) != nullptr) return OSOT_ERR_INVALID;
+    if (kind == OSOT_SHAPE_HULL) {
+        if (hull[1] < 1 || hull[1] > OSOT_KIN_MAX_HULL) { *why = "a hull has 1 .. 32 vertices"; return OSOT_ERR_INVALID; }
+        if (hull[0] < 0 || hull[0] > d->n_hull_vertices - hull[1]) { *why = "hull vertex range outside n_hull_vertices"; return OSOT_ERR_INVALID; }
+    }
+    return OSOT_OK;
+}
+}  // namespace
 
 extern "C" {
 
@@ -1165,21 +1186,40 @@ int osot_kin_create(const osot_kin_desc* d, int device, osot_kin** out) {
         const int rc = kin_check_points(d, &why);
         if (rc != OSOT_OK) return fail(rc, why);
     }
+    if (d->n_hull_vertices < 0 || d->n_hull_vertices > OSOT_KIN_MAX_HULL_VERTICES) return fail(OSOT_ERR_INVALID, "hull vertex count out of range (0..256)");
+    for (int v = 0; v < d->n_hull_vertices; ++v)
+        for (int i = 0; i < 3; ++i)
+            if (!(fabs(d->hull_vertex[v][i]) <= 1.0e300)) return fail(OSOT_ERR_INVALID, "hull vertices must be finite");
+    int n_convex = 0;
     for (int p = 0; p < d->n_pairs; ++p) {
         if (d->pair_joint[p][0] < 0 || d->pair_joint[p][0] >= d->n) return fail(OSOT_ERR_INVALID, "collision shape attached to a joint out of range");
         if (d->pair_joint[p][1] < -1 || d->pair_joint[p][1] >= d->n)      // (-1: side b is a world / environment shape)
             return fail(OSOT_ERR_INVALID, "collision shape attached to a joint out of range");
         if (!(d->pair_radius[p][0] >= 0.0) || !(d->pair_radius[p][1] >= 0.0)) return fail(OSOT_ERR_INVALID, "negative capsule radius");
-        if (d->pair_kind[p] != OSOT_SHAPE_CAPSULE && d->pair_kind[p] != OSOT_SHAPE_BOX) return fail(OSOT_ERR_UNSUPPORTED, "unknown collision shape kind");
+        if (d->pair_kind[p] < OSOT_SHAPE_CAPSULE || d->pair_kind[p] > OSOT_SHAPE_HULL || d->pair_kind_a[p] < OSOT_SHAPE_CAPSULE ||
+            d->pair_kind_a[p] > OSOT_SHAPE_HULL)
+            return fail(OSOT_ERR_UNSUPPORTED, "unknown collision shape kind");
         if (d->pair_env[p] < 0 || d->pair_env[p] > d->n_env) return fail(OSOT_ERR_INVALID, "pair refers to an environment shape out of range");
         if (d->pair_env[p] > 0 && d->pair_joint[p][1] != -1) return fail(OSOT_ERR_INVALID, "an environment shape is carried by the world (joint -1)");
-        if (d->pair_kind[p] == OSOT_SHAPE_BOX)
-            for (int i = 0; i < 3; ++i) if (!(d->pair_box[p][i] > 0.0)) return fail(OSOT_ERR_INVALID, "box half extents must be positive");
+        if (pair_is_closed_form(d, p)) {
+            if (d->pair_kind[p] == OSOT_SHAPE_BOX)
+                for (int i = 0; i < 3; ++i) if (!(d->pair_box[p][i] > 0.0)) return fail(OSOT_ERR_INVALID, "box half extents must be positive");
+            continue;
+        }
+        const char* why = "";
+        int rc = OSOT_OK;
+        if (d->pair_kind_a[p] != OSOT_SHAPE_CAPSULE)
+            rc = check_pair_shape(d, d->pair_kind_a[p], d->pair_size_a[p], d->pair_radius[p][0], d->pair_shape_R_a[p], d->pair_hull[p][0], &why);
+        if (rc == OSOT_OK && d->pair_kind[p] != OSOT_SHAPE_CAPSULE)
+            rc = check_pair_shape(d, d->pair_kind[p], d->pair_box[p], d->pair_radius[p][1], d->pair_shape_R[p], d->pair_hull[p][1], &why);
+        if (rc != OSOT_OK) return fail(rc, why);
+        ++n_convex;
     }
     DeviceGuard guard(device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
     osot_kin* k = new osot_kin();
     k->n = d->n; k->n_frames = d->n_frames; k->n_pairs = d->n_pairs; k->n_env = d->n_env; k->device = device;
+    k->n_convex = n_convex;
     hipError_t e = hipMalloc(&k->dev, sizeof(DevKin));
     if (e == hipSuccess) e = hipMemcpy(k->dev, &h, sizeof(DevKin), hipMemcpyHostToDevice);
     if (e != hipSuccess) { delete k; return fail(OSOT_ERR_HIP, hipGetErrorString(e)); }
@@ -1202,19 +1242,59 @@ int osot_kinematics(osot_kin* k, const osot_kin_batch* b, void* hip_stream) {
     if (!b->q) return fail(OSOT_ERR_INVALID, "q is null");
     DeviceGuard guard(k->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
-    const bool pairs = k->n_pairs > 0 && (b->pair_dist || b->pair_J);
+    const bool pairs = k->n_pairs > 0 && (b->pair_dist || b->pair_J || b->pair_points);
     if (pairs && k->n_env > 0 && !b->env_pose) return fail(OSOT_ERR_INVALID, "the model has environment shapes but env_pose is null");
+    const bool convex = pairs && k->n_convex > 0;      // the instantiation with the per-lane GJK: only where a pair needs it
     const dim3 grid((unsigned)(k->n <= 32 ? (b->B + 1) / 2 : b->B)), block(64);   // <= 32 joints: two instances per wavefront
     hipStream_t st = (hipStream_t)hip_stream;
     const DevKin* dk = (const DevKin*)k->dev;
     if (k->n <= 32) {
-        if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 32>), grid, block, 0, st, dk, *b);
+        if (convex) hipLaunchKernelGGL((osot_kin_kernel<true, 32, true>), grid, block, 0, st, dk, *b);
+        else if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 32>), grid, block, 0, st, dk, *b);
         else hipLaunchKernelGGL((osot_kin_kernel<false, 32>), grid, block, 0, st, dk, *b);
     } else {
-        if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 64>), grid, block, 0, st, dk, *b);
+        if (convex) hipLaunchKernelGGL((osot_kin_kernel<true, 64, true>), grid, block, 0, st, dk, *b);
+        else if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 64>), grid, block, 0, st, dk, *b);
         else hipLaunchKernelGGL((osot_kin_kernel<false, 64>), grid, block, 0, st, dk, *b);
     }
     HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// the producer's convex-shape code on the host: no device, no handle
+int osot_shape_distance(const osot_shape* a, const double* world_T_a, const osot_shape* b, const double* world_T_b, double* dist,
+                        double* ca, double* cb, int* iterations) {
+    if (!a || !b || !world_T_a || !world_T_b) return fail(OSOT_ERR_INVALID, "null argument");
+    ConvexCore C[2];
+    for (int sd = 0; sd < 2; ++sd) {
+        const osot_shape* s = sd == 0 ? a : b;
+        const double* T = sd == 0 ? world_T_a : world_T_b;
+        if (s->kind < OSOT_SHAPE_CAPSULE || s->kind > OSOT_SHAPE_HULL) return fail(OSOT_ERR_UNSUPPORTED, "unknown collision shape kind");
+        if (const char* why = convex_check_size(s->kind, s->size, s->radius)) return fail(OSOT_ERR_INVALID, why);
+        for (int i = 0; i < 12; ++i) if (!(fabs(T[i]) <= 1.0e300)) return fail(OSOT_ERR_INVALID, "collision shape: the pose must be finite");
+        if (const char* why = convex_check_rotation(T)) return fail(OSOT_ERR_INVALID, why);
+        if (s->kind == OSOT_SHAPE_HULL) {
+            if (s->n_vertices < 1 || s->n_vertices > OSOT_KIN_MAX_HULL) return fail(OSOT_ERR_INVALID, "a hull has 1 .. 32 vertices");
+            if (!s->vertices) return fail(OSOT_ERR_INVALID, "a hull without vertices");
+            for (int i = 0; i < 3 * s->n_vertices; ++i)
+                if (!(fabs(s->vertices[i]) <= 1.0e300)) return fail(OSOT_ERR_INVALID, "hull vertices must be finite");
+        }
+        if (s->kind == OSOT_SHAPE_CAPSULE) {      // axis = z of the shape frame, centred
+            const double h = s->size[2];
+            const double e0[3] = {T[9] - h * T[2], T[10] - h * T[5], T[11] - h * T[8]}, e1[3] = {T[9] + h * T[2], T[10] + h * T[5], T[11] + h * T[8]};
+            convex_segment(C[sd], e0, e1);
+        } else {
+            C[sd].kind = s->kind;
+            for (int i = 0; i < 9; ++i) C[sd].R[i] = T[i];
+            for (int i = 0; i < 3; ++i) { C[sd].p[i] = T[9 + i]; C[sd].s[i] = s->size[i]; }
+            C[sd].v = s->vertices; C[sd].nv = s->n_vertices;
+        }
+    }
+    GjkResult r;
+    gjk_closest(C[0], C[1], r);
+    if (dist) *dist = r.len - a->radius - b->radius;
+    for (int i = 0; i < 3; ++i) { if (ca) ca[i] = r.ca[i]; if (cb) cb[i] = r.cb[i]; }
+    if (iterations) *iterations = r.iterations;
     return OSOT_OK;
 }
 
@@ -1344,6 +1424,9 @@ static int control_launch(osot_solver* s, osot_kin* k, const osot_kin_batch* kb,
     if (k->n != s->plan.n) return fail(OSOT_ERR_INVALID, "the model's joint count is not the plan's variable count");
     if (k->n_pairs > 0 && (kb->pair_dist || kb->pair_J) && k->n_env > 0 && !kb->env_pose)
         return fail(OSOT_ERR_INVALID, "the model has environment shapes but env_pose is null");
+    // (the fused kernels carry the closed-form pair stage only: no instantiation of theirs runs GJK)
+    if (k->n_convex > 0 && (kb->pair_dist || kb->pair_J || kb->pair_points))
+        return fail(OSOT_ERR_UNSUPPORTED, "convex collision pairs: use osot_kinematics + osot_cycle");
     DevUpdate U;
     const char* why = "";
     int rc = make_update_args(s->plan, s->h_uplan, leaf, out, s->d_uplan, U, &why);

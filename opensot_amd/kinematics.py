@@ -36,7 +36,9 @@ class KinModel:
     # environment shapes and link-vs-environment pairs (CollisionAvoidance::addCollisionShape / moveCollisionShape /
     # setLinksVsEnvironment, CollisionAvoidance.h:115-144).  link_shapes: link name -> (joint, a0, a1, radius), the capsule
     # a link is checked with; env_shapes: dicts (name, link, kind, data ..., pose); self_pairs: the link-link pairs that
-    # stay in front of the generated link-environment pairs
+    # stay in front of the generated link-environment pairs.  A link shape may also be a dict, any convex shape in its link frame:
+    # dict(joint=index or name, kind="capsule" | "box" | "cylinder" | "hull", a0=, a1= | half= | size=(radius, 0, half length) |
+    # verts=[nv][3], r=rounding radius (0), R=eye(3), p=zeros(3)) -- the keys add_collision_shape gives an environment shape
     link_shapes: dict = field(default_factory=dict)
     env_shapes: list = field(default_factory=list)
     self_pairs: list = None
@@ -79,7 +81,8 @@ class KinModel:
         """CollisionAvoidance::addCollisionShape(name, link, shape, link_T_shape) (CollisionAvoidance.cpp:166-173).  link:
         "world" (an environment shape, movable afterwards) or a joint / link name of the model.  shape: ("sphere", r),
         ("capsule", length, r) (axis = z of the shape frame, centred, like XBot::Collision::Shape::Capsule) or
-        ("box", (sx, sy, sz)) (full sizes).  link_T_shape: (R[3][3], p[3]), default identity.  False if the name is taken
+        ("box", (sx, sy, sz)) (full sizes), ("cylinder", length, r) (axis = z, centred) or ("convex", vertices[nv][3]) (the convex
+        hull of 1 .. 32 points: a convex mesh).  link_T_shape: (R[3][3], p[3]), default identity.  False if the name is taken
         or the link unknown (the reference returns false as well)."""
         if any(e["name"] == name for e in self.env_shapes):
             return False
@@ -95,8 +98,16 @@ class KinModel:
             e = dict(kind="capsule", a0=np.array([0, 0, -0.5 * L]), a1=np.array([0, 0, 0.5 * L]), r=r)
         elif kind == "box":
             e = dict(kind="box", half=0.5 * np.asarray(shape[1], float).reshape(3), r=0.0)
+        elif kind == "cylinder":
+            L, r = float(shape[1]), float(shape[2])
+            e = dict(kind="cylinder", size=np.array([r, 0.0, 0.5 * L]), r=0.0)
+        elif kind == "convex":
+            V = np.asarray(shape[1], float).reshape(-1, 3)
+            if not 1 <= len(V) <= abi.KIN_MAX_HULL:
+                raise ValueError(f"a convex shape is the hull of 1 .. {abi.KIN_MAX_HULL} vertices, not {len(V)}")
+            e = dict(kind="hull", verts=V.copy(), r=0.0)
         else:
-            raise ValueError("shape must be a sphere, a capsule or a box (meshes / box-box pairs are not offered)")
+            raise ValueError("shape must be a sphere, a capsule, a box, a cylinder or a convex vertex set (non-convex meshes are not offered)")
         e.update(name=name, link=link, R=R, p=p)
         self.env_shapes.append(e)
         self._rebuild_pairs()
@@ -116,7 +127,7 @@ class KinModel:
         checked against every environment shape; the pair list becomes self_pairs + links x environment"""
         missing = [l for l in links if l not in self.link_shapes]
         if missing:
-            raise KeyError(f"no collision capsule known for {missing}")
+            raise KeyError(f"no collision shape known for {missing}")
         self.env_links = list(links)
         self._rebuild_pairs()
 
@@ -128,6 +139,45 @@ class KinModel:
             out[k, :9] = e["R"].reshape(9); out[k, 9:] = e["p"]
         return out
 
+    _KIND = {"capsule": abi.SHAPE_CAPSULE, "box": abi.SHAPE_BOX, "cylinder": abi.SHAPE_CYLINDER, "hull": abi.SHAPE_HULL}
+
+    @staticmethod
+    def _size(e):
+        return np.asarray(e["half"] if e["kind"] == "box" else e.get("size", np.zeros(3)), float).reshape(3)
+
+    def _convex_pair(self, A, jb, env, B, R, p):
+        """the pair tuple of a link shape given as a dict (A) against the shape dict B carried by joint jb / the world / an
+        environment slot, with (R, p) = carrier_T_shape of B"""
+        ja = A["joint"]
+        ja = self.names.index(ja) if isinstance(ja, str) else int(ja)
+        Ra, pa = np.asarray(A.get("R", np.eye(3)), float).reshape(3, 3), np.asarray(A.get("p", np.zeros(3)), float).reshape(3)
+        z = (0.0, 0.0, 0.0)
+        ex = dict(env=env)
+        if A["kind"] == "capsule":
+            a0, a1 = Ra @ np.asarray(A["a0"], float) + pa, Ra @ np.asarray(A["a1"], float) + pa
+        else:
+            a0 = a1 = z
+            ex.update(kind_a=self._KIND[A["kind"]], size_a=self._size(A), R_a=Ra, p_a=pa, hull_a=A.get("verts"))
+        if B["kind"] == "capsule":
+            b0, b1 = R @ np.asarray(B["a0"], float) + p, R @ np.asarray(B["a1"], float) + p
+            ex.update(kind=abi.SHAPE_CAPSULE)
+        else:
+            b0 = b1 = z
+            ex.update(kind=self._KIND[B["kind"]], half=self._size(B), R=R, p=p, hull=B.get("verts"))
+        return (ja, a0, a1, float(A.get("r", 0.0)), jb, b0, b1, float(B.get("r", 0.0)), ex)
+
+    def link_pair(self, a, b):
+        """the pair tuple of two entries of link_shapes (for `pairs` / `self_pairs`): any shape against any shape"""
+        A, Bs = self.link_shapes[a], self.link_shapes[b]
+        if not isinstance(A, dict) and not isinstance(Bs, dict):
+            return tuple(A) + tuple(Bs)
+        as_dict = lambda s: s if isinstance(s, dict) else dict(joint=s[0], kind="capsule", a0=s[1], a1=s[2], r=s[3])
+        A, Bs = as_dict(A), as_dict(Bs)
+        jb = Bs["joint"]
+        jb = self.names.index(jb) if isinstance(jb, str) else int(jb)
+        return self._convex_pair(A, jb, 0, Bs, np.asarray(Bs.get("R", np.eye(3)), float).reshape(3, 3),
+                                 np.asarray(Bs.get("p", np.zeros(3)), float).reshape(3))
+
     def _rebuild_pairs(self):
         if self.self_pairs is None:
             self.self_pairs = list(self.pairs)
@@ -135,7 +185,12 @@ class KinModel:
         names = list(getattr(self, "pair_names", [])[:len(self.self_pairs)])
         world = [e for e in self.env_shapes if e["link"] == "world"]
         for ln in self.env_links:
-            ja, a0, a1, ra = self.link_shapes[ln]
+            general = isinstance(self.link_shapes[ln], dict)
+            if general:
+                ja = self.link_shapes[ln]["joint"]
+                ja = self.names.index(ja) if isinstance(ja, str) else int(ja)
+            else:
+                ja, a0, a1, ra = self.link_shapes[ln]
             for e in self.env_shapes:
                 if e["link"] == "world":
                     slot = [w["name"] for w in world].index(e["name"])
@@ -144,7 +199,10 @@ class KinModel:
                     jb, env, R, p = self.names.index(e["link"]), 0, e["R"], e["p"]
                     if jb == ja:
                         continue
-                if e["kind"] == "box":
+                if general or e["kind"] in ("cylinder", "hull"):
+                    A = self.link_shapes[ln] if general else dict(joint=ja, kind="capsule", a0=a0, a1=a1, r=ra)
+                    pairs.append(self._convex_pair(A, jb, env, e, R, p))
+                elif e["kind"] == "box":
                     pairs.append((ja, a0, a1, ra, jb, (0, 0, 0), (0, 0, 0), e["r"],
                                   dict(kind=abi.SHAPE_BOX, env=env, half=e["half"], R=R, p=p)))
                 else:
@@ -196,6 +254,23 @@ class KinModel:
                 d.point_p[i][c] = float(p[c])
         d.n_pairs = len(self.pairs)
         d.n_env = sum(1 for e in self.env_shapes if e["link"] == "world")
+        hulls = {}      # vertex bytes -> first vertex: a hull that several pairs share is stored once
+
+        def hull_range(V):
+            V = np.ascontiguousarray(np.asarray(V, float).reshape(-1, 3))
+            if not 1 <= len(V) <= abi.KIN_MAX_HULL:
+                raise ValueError(f"a hull has 1 .. {abi.KIN_MAX_HULL} vertices, not {len(V)}")
+            key = V.tobytes()
+            if key not in hulls:
+                first = d.n_hull_vertices
+                if first + len(V) > abi.KIN_MAX_HULL_VERTICES:
+                    raise ValueError(f"the producer holds {abi.KIN_MAX_HULL_VERTICES} hull vertices")
+                for v in range(len(V)):
+                    for i in range(3):
+                        d.hull_vertex[first + v][i] = float(V[v, i])
+                d.n_hull_vertices = first + len(V)
+                hulls[key] = first
+            return hulls[key], len(V)
         for k, pr in enumerate(self.pairs):
             ja, a0, a1, ra, jb, b0, b1, rb = pr[:8]
             ex = pr[8] if len(pr) > 8 else {}
@@ -213,6 +288,19 @@ class KinModel:
                 d.pair_shape_R[k][i] = float(R[i])
             for i in range(3):
                 d.pair_shape_p[k][i] = float(pp[i]); d.pair_box[k][i] = float(hf[i])
+            if d.pair_kind[k] == abi.SHAPE_HULL:
+                d.pair_hull[k][1][0], d.pair_hull[k][1][1] = hull_range(ex["hull"])
+            d.pair_kind_a[k] = int(ex.get("kind_a", abi.SHAPE_CAPSULE))
+            if d.pair_kind_a[k] != abi.SHAPE_CAPSULE:
+                Ra = np.asarray(ex.get("R_a", np.eye(3)), float).reshape(9)
+                pa = np.asarray(ex.get("p_a", np.zeros(3)), float)
+                sa = np.asarray(ex.get("size_a", np.zeros(3)), float)
+                for i in range(9):
+                    d.pair_shape_R_a[k][i] = float(Ra[i])
+                for i in range(3):
+                    d.pair_shape_p_a[k][i] = float(pa[i]); d.pair_size_a[k][i] = float(sa[i])
+                if d.pair_kind_a[k] == abi.SHAPE_HULL:
+                    d.pair_hull[k][0][0], d.pair_hull[k][0][1] = hull_range(ex["hull_a"])
         return d
 
 
@@ -335,19 +423,22 @@ class Kinematics:
             pass
 
     def forward(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None,
-                batch=None):
+                batch=None, pair_points=None):
         """osot_kinematics for the batch `batch_args` describes, stream-ordered on torch's current stream (batch: a batch_args()
         result to reuse)"""
-        kb = batch if batch is not None else self.batch_args(q, frame_pose, frame_J, com, com_J, pair_dist, pair_J, env_pose, points)
+        kb = batch if batch is not None else self.batch_args(q, frame_pose, frame_J, com, com_J, pair_dist, pair_J, env_pose, points,
+                                                                      pair_points)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         abi.check(self._lib.osot_kinematics(self._h, C.byref(kb), stream), "osot_kinematics")
 
-    def batch_args(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None):
+    def batch_args(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None,
+                   pair_points=None):
         """the osot_kin_batch of a call (pointers and strides only; the tensors must outlive its use).  q [B][n] (device).  frame_pose: {frame index: tensor [B][12]}; frame_J: {frame index: (A_k tensor [B][ma][n],
         first row)}; com: tensor [B][3]; com_J: (A_k tensor, first row).
         env_pose: poses of the environment shapes, a device tensor [n_env][12] (one world for all instances) or
         [B][n_env][12]; default: the model's own (add_collision_shape / move_collision_shape), uploaded when they change.
-        points: tensor [B][n_points][3], the world positions of the model's contact points (add_point)"""
+        points: tensor [B][n_points][3], the world positions of the model's contact points (add_point)
+        pair_points: tensor [B][n_pairs][6], the witness points ca, cb of every pair (world, on the cores)"""
         B, n = q.shape
         assert n == self.model.n and q.is_contiguous()
         kb = abi.KinBatch()
@@ -379,8 +470,12 @@ class Kinematics:
             assert A.is_contiguous() and A.shape[2] == n and row + len(self.model.pairs) <= A.shape[1]
             kb.pair_J = A.data_ptr() + 8 * row * n
             kb.pair_J_stride = A.shape[1] * n
+        if pair_points is not None:
+            assert pair_points.is_contiguous() and pair_points.dtype == torch.float64 and pair_points.shape[0] >= B
+            assert tuple(pair_points.shape[1:]) == (len(self.model.pairs), 6)
+            kb.pair_points = pair_points.data_ptr()
         n_env = sum(1 for e in self.model.env_shapes if e["link"] == "world")
-        if n_env and (pair_dist is not None or pair_J is not None):
+        if n_env and (pair_dist is not None or pair_J is not None or pair_points is not None):
             if env_pose is None:
                 host = self.model.env_pose_array()
                 if self._env_host is None or not np.array_equal(host, self._env_host):
