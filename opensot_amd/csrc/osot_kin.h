@@ -119,6 +119,24 @@ __device__ inline void closest_segment_points(const double* p1, const double* q1
         t = (b * s + f) / e;
         if (t < 0.0) { t = 0.0; s = clamp01(-c / a); }
         else if (t > 1.0) { t = 1.0; s = clamp01((b - c) / a); }
+        // Near-parallel axes (under 1e-5 rad): below about 3e-7 rad den is the round-off of a e - b^2 and s is chance; where t then
+        // stays inside (0, 1) the pair above can be the wrong end of the overlap, too long by the angle times the overlap.  A
+        // minimiser of two such segments has an end point of one of them, so the four end-point projections are tried as well.
+        // One is taken only where it is shorter beyond round-off: parallel axes keep the pair they had, bit for bit.
+        if (!(den > 1.0e-10 * a * e)) {
+            double w[3] = {r[0] + s * d1[0] - t * d2[0], r[1] + s * d1[1] - t * d2[1], r[2] + s * d1[2] - t * d2[2]};
+            double best = (w[0] * w[0] + w[1] * w[1] + w[2] * w[2]) * (1.0 - 1.0e-14);
+#pragma unroll 1
+            for (int k = 0; k < 4; ++k) {
+                const double fix = (k & 1) ? 1.0 : 0.0;
+                const double sk = (k < 2) ? fix : clamp01((b * fix - c) / a);
+                const double tk = (k < 2) ? clamp01((b * fix + f) / e) : fix;
+#pragma unroll
+                for (int i = 0; i < 3; ++i) w[i] = r[i] + sk * d1[i] - tk * d2[i];
+                const double dk = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+                if (dk < best) { best = dk; s = sk; t = tk; }
+            }
+        }
     }
 #pragma unroll
     for (int i = 0; i < 3; ++i) { c1[i] = p1[i] + s * d1[i]; c2[i] = p2[i] + t * d2[i]; }

@@ -97,6 +97,16 @@ def closest_segment_points(p1, q1, p2, q2):
             t, s = 0.0, cl(-c / a)
         elif t > 1.0:
             t, s = 1.0, cl((b - c) / a)
+        if not den > 1e-10 * a * e:
+            # near-parallel axes: den is round-off below about 3e-7 rad and s chance, so the pair above can be the wrong end of the
+            # overlap (too long by the angle times the overlap).  A minimiser then has an end point of one segment: the four
+            # end-point projections are tried as well, and taken only where shorter beyond round-off
+            w = r + s * d1 - t * d2
+            best = (w @ w) * (1.0 - 1e-14)
+            for sk, tk in ((0.0, cl(f / e)), (1.0, cl((b + f) / e)), (cl(-c / a), 0.0), (cl((b - c) / a), 1.0)):
+                w = r + sk * d1 - tk * d2
+                if w @ w < best:
+                    best, s, t = w @ w, sk, tk
     return p1 + s * d1, p2 + t * d2
 
 

@@ -511,15 +511,9 @@ def test_control_cycle_in_one_launch_matches_the_three_calls(mode, gpu_device):
     and "dense_weight" (Task::setWeight(W)) through the EXTRA instantiation; round 6 -- "relative_base": DefaultHumanoidStack's
     waist2LeftArm / waist2RightArm / right2LeftLeg (Cartesian tasks with a base link, Cartesian.cpp:73-81) produced inside the launch.
     An odd batch."""
-    import torch
-    from opensot_amd.plan import Rows
-    from opensot_amd.solver import BatchedStack
     pairs = mode == "collision_pairs"
     m = kin.humanoid32_pairs(kin.humanoid32()) if pairs else (_relative_model() if mode == "relative_base" else kin.humanoid32())
     n, B = m.n, 203
-    P = len(m.pairs) if pairs else 0
-    dev = torch.device("cuda", 0)
-    f64 = dict(dtype=torch.float64, device=dev)
     rng = np.random.default_rng(19)
     q0 = np.zeros((B, n))
     q0[:, [m.names.index(s + "KneeSag") for s in "RL"]] = 0.5
@@ -529,6 +523,20 @@ def test_control_cycle_in_one_launch_matches_the_three_calls(mode, gpu_device):
     if pairs:
         q0[:, m.names.index("RShLat")] = -0.35; q0[:, m.names.index("LShLat")] = 0.35
     q0 += rng.normal(0.0, 0.02, (B, n))
+    control_cycle_matches_the_three_calls(m, mode, q0, rng)
+
+
+def control_cycle_matches_the_three_calls(m, mode, q0, rng):
+    """the body of the test above for any model with four frames (tests/test_tree_limits_gpu.py runs it on trees of 20 and 40 joints):
+    the plan, the three runs from q0 [B][n] and every comparison; rng: the generator the random inputs are drawn from"""
+    import torch
+    from opensot_amd.plan import Rows
+    from opensot_amd.solver import BatchedStack
+    pairs = mode == "collision_pairs"
+    B, n = q0.shape
+    P = len(m.pairs) if pairs else 0
+    dev = torch.device("cuda", 0)
+    f64 = dict(dtype=torch.float64, device=dev)
     Wd = None
     if mode == "dense_weight":
         Mw = rng.normal(size=(6, 6)); Wd = Mw @ Mw.T / 6.0 + np.eye(6)
