@@ -650,6 +650,7 @@ int osot_qp_solve_batch_admm_warm(int B, int n, int nc, const double* H, const d
 #define OSOT_KIN_MAX_POINTS 16
 #define OSOT_KIN_MAX_HULL_VERTICES 256
 #define OSOT_KIN_MAX_HULL 32                 /* vertices of ONE hull */
+#define OSOT_KIN_MAX_ROWSETS 8
 enum { OSOT_JOINT_REVOLUTE = 0, OSOT_JOINT_PRISMATIC = 1 };
 typedef struct {
     int n;                                   /* joints = generalised coordinates; tree order: parent[j] < j     */
@@ -733,6 +734,47 @@ typedef struct {
     int pair_hull[OSOT_KIN_MAX_PAIRS][2][2];
     int n_hull_vertices;                         /* 0 .. OSOT_KIN_MAX_HULL_VERTICES                                   */
     double hull_vertex[OSOT_KIN_MAX_HULL_VERTICES][3];
+    /* ROW SETS (velocity::Contact, velocity::PureRolling / PureRollingPosition / PureRollingOrientation, floating_base::Contact,
+     * constraints::velocity::OmniWheels4X): up to 6 rows derived from ONE frame, "a small pose-dependent matrix times the frame's
+     * Jacobian", written per instance straight into a level's A_k or a row block's C (osot_kin_batch.rowset_A), as frame_J is.
+     * rowset_row_mask: bit r set = row r of the kind is written; the rows are written COMPACTLY, in order (PureRollingPosition =
+     * rows {0, 1[, 2]}, PureRollingOrientation = row {3} of OSOT_ROWSET_PURE_ROLLING, PureRolling.cpp:89-150).  All of them use the
+     * frame's WORLD pose and world Jacobian [linear; angular], whatever frame_body / frame_col_mask say; a frame with
+     * frame_base != 0 is refused.
+     *   OSOT_ROWSET_CONTACT (src/tasks/velocity/Contact.cpp:19-33): A = K Ad(R_f') J_f, both 3-row blocks of J_f rotated by R_f'
+     *     (XBot::Utils::rotate); K = rowset_param[0 .. 35], 6 x 6 row-major, row r of it is row r of the kind.  b = 0 is the
+     *     caller's: the block is an OSOT_TASK_GENERIC.
+     *     rowset_split = 1 (src/tasks/floating_base/Contact.cpp:47-67 with lambda = 0, the reference's default): the rows are
+     *     written with SIX columns, A = (K Ad(R_f') J_f)[:, 0:6], for a 6-variable plan, and osot_kin_batch.rowset_b receives
+     *     b = -(K Ad(R_f') J_f)[:, 6:] qdot[6:].  The lambda * error term of that task is NOT produced.  Needs n > 6.
+     *   OSOT_ROWSET_PURE_ROLLING (src/tasks/velocity/PureRolling.cpp:50-77): 4 rows.  rowset_param = {radius r, outward normal
+     *     n[3] (unit, world), S33[9] row-major}.  d = -r n; Jc = [J_lin + J_ang x d; J_ang], the Jacobian of the contact point
+     *     p_f - r n; a = (R_f e_z) x n, normalised (the wheel spins about its local z); A = S Jc with S = [S33 0; 0 0 0 a'].
+     *     S33 comes from osot_pure_rolling_s33 below.  NO GUARD for a wheel axis parallel to n: a is 0 / 0 there, as in the
+     *     reference (PureRolling.cpp:64-65).
+     *   OSOT_ROWSET_OMNI4X (src/constraints/velocity/OmniWheels4X.cpp:22-74): 3 rows.  rowset_param = {l1, l2, r}; rowset_wheel =
+     *     the coordinates of the front-left, front-right, hind-left, hind-right wheel joints (each 6 .. n - 1); rowset_frame = the
+     *     base link frame.  Columns 0 .. 5 are the constant selection (0,0) = (1,1) = (2,5) = 1; columns >= 6 are
+     *     R_base (r / 4) v_j with v_j = 0 except fl: -(1, -1, -1/(l1+l2)), fr: -(1, 1, 1/(l1+l2)), hl: -(1, 1, -1/(l1+l2)),
+     *     hr: -(1, -1, 1/(l1+l2)).  The caller puts the rows in an OSOT_ROWS_GENERIC block with lo = up = 0.
+     * GAZE REFERENCES (src/tasks/velocity/Gaze.cpp:52-74, src/utils/cartesian_utils.cpp:27-35): per gaze g, with [R | p] the pose
+     * frame gaze_frame[g] publishes (world, or relative to its frame_base) and the point osot_kin_batch.gaze_point[g]:
+     * t = R'(point - p); where |t| >= 0.2 (GAZE_THRESHOLD) osot_kin_batch.gaze_ref[g] is overwritten with [RotZ(pan) RotY(-tilt) | 0],
+     * pan = atan2(t_y, t_x), tilt = atan2(t_z, sqrt(t_y^2 + t_x^2)) (_bl_T_gaze_kdl is never set in the reference: the identity);
+     * where |t| < 0.2 the buffer is left untouched, bit for bit: it is the previous reference.  The task itself is an
+     * OSOT_TASK_CARTESIAN with the SubTask row mask {4, 5} reading gaze_ref as its reference pose.
+     * A model with row sets or gaze references is served by osot_kinematics; osot_control_cycle / osot_control_rollout refuse it,
+     * and so does osot_kinematics when convex (GJK) pair outputs are bound in the same call (OSOT_ERR_UNSUPPORTED).
+     * All zero = none.  (Like the convex block, this one sits in front of the contact points, which stay the struct's last members.) */
+    int n_rowsets;                               /* 0 .. OSOT_KIN_MAX_ROWSETS                                         */
+    int rowset_kind[OSOT_KIN_MAX_ROWSETS];       /* OSOT_ROWSET_*                                                     */
+    int rowset_frame[OSOT_KIN_MAX_ROWSETS];      /* 0 .. n_frames - 1                                                 */
+    int rowset_row_mask[OSOT_KIN_MAX_ROWSETS];   /* rows of the kind (6 / 4 / 3) that are written; not empty          */
+    int rowset_split[OSOT_KIN_MAX_ROWSETS];      /* OSOT_ROWSET_CONTACT only                                          */
+    int rowset_wheel[OSOT_KIN_MAX_ROWSETS][4];   /* OSOT_ROWSET_OMNI4X only                                           */
+    double rowset_param[OSOT_KIN_MAX_ROWSETS][36];
+    int n_gaze;                                  /* 0 .. OSOT_KIN_MAX_FRAMES                                          */
+    int gaze_frame[OSOT_KIN_MAX_FRAMES];         /* 0 .. n_frames - 1                                                 */
     /* CONTACT POINTS (velocity::ConvexHull: convex_hull::getSupportPolygonPoints asks the model for getPose(link).translation() of
      * every link in contact, src/utils/convex_hull_utils.cpp:142-174): point i is fixed at point_p[i] in the frame of joint
      * point_joint[i]'s link; the producer writes its world position to osot_kin_batch.points.  All zero = none. */
@@ -740,6 +782,7 @@ typedef struct {
     int point_joint[OSOT_KIN_MAX_POINTS];        /* 0 .. n - 1                                                        */
     double point_p[OSOT_KIN_MAX_POINTS][3];
 } osot_kin_desc;
+enum { OSOT_ROWSET_CONTACT = 1, OSOT_ROWSET_PURE_ROLLING = 2, OSOT_ROWSET_OMNI4X = 3 };
 enum { OSOT_SHAPE_CAPSULE = 0, OSOT_SHAPE_BOX = 1, OSOT_SHAPE_CYLINDER = 2, OSOT_SHAPE_HULL = 3 };
 #define OSOT_KIN_MAX_ENV 16
 typedef struct {
@@ -762,6 +805,15 @@ typedef struct {
                                                       world and ON THE CORES (the capsule axis, the box, the hull: not the
                                                       rounded surface) -- what the reference's collision module returns next to
                                                       the distance; or NULL                                          */
+    /* row sets (osot_kin_desc.n_rowsets): all NULL / 0 = none written.  (In front of `points`, which stays the last member.) */
+    double* rowset_A[OSOT_KIN_MAX_ROWSETS];          /* first written row of set s in instance 0, or NULL; row length n (6 with
+                                                        rowset_split)                                                 */
+    long long rowset_A_stride[OSOT_KIN_MAX_ROWSETS]; /* doubles from one instance to the next                         */
+    double* rowset_b[OSOT_KIN_MAX_ROWSETS];          /* rowset_split only: first entry of b in instance 0, or NULL    */
+    long long rowset_b_stride[OSOT_KIN_MAX_ROWSETS];
+    const double* rowset_qdot;                       /* [B][n] joint velocities: required where a rowset_b is bound   */
+    const double* gaze_point[OSOT_KIN_MAX_FRAMES];   /* [B][3] the point gaze g looks at, in the coordinates of the pose */
+    double* gaze_ref[OSOT_KIN_MAX_FRAMES];           /* [B][12] read-modify-write: the Cartesian leaf's reference pose  */
     double* points;                                /* [B][n_points][3] world positions of the contact points (the
                                                       OSOT_ROWS_CONVEX_HULL leaf p2), or NULL                        */
 } osot_kin_batch;
@@ -769,6 +821,12 @@ typedef struct osot_kin osot_kin;
 int osot_kin_create(const osot_kin_desc* desc, int device, osot_kin** out);
 int osot_kin_destroy(osot_kin* k);
 int osot_kinematics(osot_kin* k, const osot_kin_batch* batch, void* hip_stream);
+/* The 3 x 3 block S33 of OSOT_ROWSET_PURE_ROLLING for the outward normal n (HOST only, no device): PureRolling::setOutwardNormal
+ * (src/tasks/velocity/PureRolling.cpp:19-47) as it is written.  uz = n / |n|; ux = e1, then e2 where |uz . e2| < |uz . ux|, then e3
+ * where |uz . e3| < |uz . ux| with the ux chosen so far (a SEQUENTIAL choice); uy = uz x ux (ux is not made orthogonal to uz, so uy
+ * is not a unit vector in general).  _local_R_world has the ROWS ux, uy, uz and _update() applies its transpose: S33's COLUMNS are
+ * ux, uy, uz.  s33 [9] row-major; normal_unit [3] (may be NULL) receives uz.  OSOT_ERR_INVALID: a null or zero normal. */
+int osot_pure_rolling_s33(const double* normal, double* s33, double* normal_unit);
 /* Distance of two convex shapes ON THE HOST (no device is touched): the code the producer's lanes run, for a setup-time check
  * ("do my shapes overlap at q0?").  size as in the CONVEX SHAPES block above; a capsule: size[2] = half length along z of the shape frame;
  * world_T_a / world_T_b: [R row-major | p], 12 doubles.  Always GJK, also for the pairs the producer has a closed form for.

@@ -127,6 +127,9 @@ KIN_MAX_POINTS = 16
 KIN_MAX_HULL_VERTICES, KIN_MAX_HULL = 256, 32      # hull vertices of a model / of one hull
 SHAPE_CAPSULE, SHAPE_BOX, SHAPE_CYLINDER, SHAPE_HULL = 0, 1, 2, 3
 JOINT_REVOLUTE, JOINT_PRISMATIC = 0, 1
+KIN_MAX_ROWSETS = 8
+ROWSET_CONTACT, ROWSET_PURE_ROLLING, ROWSET_OMNI4X = 1, 2, 3
+ROWSET_ROWS = {ROWSET_CONTACT: 6, ROWSET_PURE_ROLLING: 4, ROWSET_OMNI4X: 3}      # rows of a kind before its row_mask
 
 
 class KinDesc(C.Structure):
@@ -148,6 +151,10 @@ class KinDesc(C.Structure):
                 ("pair_shape_R_a", (C.c_double * 9) * KIN_MAX_PAIRS), ("pair_shape_p_a", (C.c_double * 3) * KIN_MAX_PAIRS),
                 ("pair_hull", ((C.c_int * 2) * 2) * KIN_MAX_PAIRS), ("n_hull_vertices", C.c_int),
                 ("hull_vertex", (C.c_double * 3) * KIN_MAX_HULL_VERTICES),
+                ("n_rowsets", C.c_int), ("rowset_kind", C.c_int * KIN_MAX_ROWSETS), ("rowset_frame", C.c_int * KIN_MAX_ROWSETS),
+                ("rowset_row_mask", C.c_int * KIN_MAX_ROWSETS), ("rowset_split", C.c_int * KIN_MAX_ROWSETS),
+                ("rowset_wheel", (C.c_int * 4) * KIN_MAX_ROWSETS), ("rowset_param", (C.c_double * 36) * KIN_MAX_ROWSETS),
+                ("n_gaze", C.c_int), ("gaze_frame", C.c_int * KIN_MAX_FRAMES),
                 ("n_points", C.c_int), ("point_joint", C.c_int * KIN_MAX_POINTS), ("point_p", (C.c_double * 3) * KIN_MAX_POINTS)]
 
 
@@ -157,6 +164,9 @@ class KinBatch(C.Structure):
                 ("com", C.c_void_p), ("com_J", C.c_void_p), ("com_J_stride", C.c_longlong),
                 ("pair_dist", C.c_void_p), ("pair_J", C.c_void_p), ("pair_J_stride", C.c_longlong),
                 ("env_pose", C.c_void_p), ("env_pose_stride", C.c_longlong), ("pair_points", C.c_void_p),
+                ("rowset_A", C.c_void_p * KIN_MAX_ROWSETS), ("rowset_A_stride", C.c_longlong * KIN_MAX_ROWSETS),
+                ("rowset_b", C.c_void_p * KIN_MAX_ROWSETS), ("rowset_b_stride", C.c_longlong * KIN_MAX_ROWSETS),
+                ("rowset_qdot", C.c_void_p), ("gaze_point", C.c_void_p * KIN_MAX_FRAMES), ("gaze_ref", C.c_void_p * KIN_MAX_FRAMES),
                 ("points", C.c_void_p)]
 
 
@@ -203,7 +213,7 @@ SYMBOLS = [
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
-    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
+    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_pure_rolling_s33", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
     "osot_grad_create", "osot_grad_destroy", "osot_posture_gradient", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
     "osot_backend_create", "osot_backend_destroy", "osot_backend_init_problem",
     "osot_backend_update_task", "osot_backend_update_constraints", "osot_backend_update_bounds",
@@ -281,6 +291,7 @@ def lib():
     L.osot_kin_create.argtypes = [C.POINTER(KinDesc), C.c_int, C.POINTER(vp)]
     L.osot_kin_destroy.argtypes = [vp]
     L.osot_kinematics.argtypes = [vp, C.POINTER(KinBatch), vp]
+    L.osot_pure_rolling_s33.argtypes = [dp, dp, dp]
     L.osot_shape_distance.argtypes = [C.POINTER(Shape), dp, C.POINTER(Shape), dp, dp, dp, dp, ip]
     L.osot_dyn_create.argtypes = [C.POINTER(KinDesc), C.POINTER(DynDesc), C.c_int, C.POINTER(vp)]
     L.osot_dyn_destroy.argtypes = [vp]

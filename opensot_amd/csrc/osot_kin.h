@@ -22,6 +22,7 @@
 #include <osot_team.h>
 #include <osot_mi355x.h>
 #include <osot_convex.h>
+#include <cmath>
 
 namespace osot {
 
@@ -34,6 +35,7 @@ struct DevKin {            // osot_kin_desc + ancestor masks, in device memory
     // subtree aggregate is a DIFFERENCE OF PREFIX SUMS over that order (the centre-of-mass Jacobian, stage 4)
     int dfs_pos[OSOT_KIN_MAX_JOINTS];
     int sub_end[OSOT_KIN_MAX_JOINTS];
+    unsigned rowset_frames;    // bit f set: a row set hangs on frame f (the ROWS instantiation computes its column without a frame_J)
 };
 
 // the tables derived from the tree (h.d set, parent[j] < j checked by the caller): shared by osot_kin_create and the emulator's driver
@@ -47,6 +49,9 @@ inline void kin_build_tables(DevKin& h) {
         h.total_mass += h.d.mass[j];
     }
     if (!(h.total_mass > 0.0)) h.total_mass = 1.0;
+    h.rowset_frames = 0u;
+    for (int s = 0; s < h.d.n_rowsets && s < OSOT_KIN_MAX_ROWSETS; ++s)
+        if (h.d.rowset_frame[s] >= 0 && h.d.rowset_frame[s] < OSOT_KIN_MAX_FRAMES) h.rowset_frames |= 1u << h.d.rowset_frame[s];
     int next_child[OSOT_KIN_MAX_JOINTS], root_off = 0;      // parents come before their children: one pass
     for (int j = 0; j < n; ++j) {
         const int size = __builtin_popcountll(h.sub[j]), pa = h.d.parent[j];
@@ -75,6 +80,45 @@ inline int kin_check_points(const osot_kin_desc* d, const char** why) {
     if (d->n_points < 0 || d->n_points > OSOT_KIN_MAX_POINTS) { *why = "contact point count out of range (0..16)"; return OSOT_ERR_INVALID; }
     for (int i = 0; i < d->n_points; ++i)
         if (d->point_joint[i] < 0 || d->point_joint[i] >= d->n) { *why = "contact point attached to a joint out of range"; return OSOT_ERR_INVALID; }
+    return OSOT_OK;
+}
+
+// ... and of the row sets and gaze references (osot_kin_desc.rowset_*, gaze_*); kin_check_frames has passed
+__host__ __device__ inline int kin_rowset_rows(int kind) { return kind == OSOT_ROWSET_CONTACT ? 6 : (kind == OSOT_ROWSET_PURE_ROLLING ? 4 : 3); }
+inline int kin_check_rowsets(const osot_kin_desc* d, const char** why) {
+    if (d->n_rowsets < 0 || d->n_rowsets > OSOT_KIN_MAX_ROWSETS) { *why = "row set count out of range (0..8)"; return OSOT_ERR_INVALID; }
+    if (d->n_gaze < 0 || d->n_gaze > OSOT_KIN_MAX_FRAMES) { *why = "gaze count out of range (0..8)"; return OSOT_ERR_INVALID; }
+    for (int s = 0; s < d->n_rowsets; ++s) {
+        const int kind = d->rowset_kind[s], f = d->rowset_frame[s];
+        if (kind != OSOT_ROWSET_CONTACT && kind != OSOT_ROWSET_PURE_ROLLING && kind != OSOT_ROWSET_OMNI4X) { *why = "unknown row set kind"; return OSOT_ERR_INVALID; }
+        if (f < 0 || f >= d->n_frames) { *why = "row set on a frame out of range"; return OSOT_ERR_INVALID; }
+        if (d->frame_base[f] != 0) { *why = "a row set uses the world pose and Jacobian of its frame: frame_base must be 0"; return OSOT_ERR_INVALID; }
+        if (d->rowset_row_mask[s] == 0) { *why = "row set with an empty row_mask"; return OSOT_ERR_INVALID; }
+        if (d->rowset_row_mask[s] < 0 || (d->rowset_row_mask[s] >> kin_rowset_rows(kind)) != 0) { *why = "row_mask names a row the kind does not have"; return OSOT_ERR_INVALID; }
+        if (d->rowset_split[s] != 0 && kind != OSOT_ROWSET_CONTACT) { *why = "only a contact row set can be split"; return OSOT_ERR_INVALID; }
+        if (d->rowset_split[s] != 0 && d->n <= 6) { *why = "a split contact needs more than 6 coordinates"; return OSOT_ERR_INVALID; }
+        if (kind == OSOT_ROWSET_OMNI4X)
+            for (int w = 0; w < 4; ++w)
+                if (d->rowset_wheel[s][w] < 6 || d->rowset_wheel[s][w] >= d->n) { *why = "wheel coordinate out of range (6 .. n - 1)"; return OSOT_ERR_INVALID; }
+    }
+    for (int g = 0; g < d->n_gaze; ++g)
+        if (d->gaze_frame[g] < 0 || d->gaze_frame[g] >= d->n_frames) { *why = "gaze on a frame out of range"; return OSOT_ERR_INVALID; }
+    return OSOT_OK;
+}
+// PureRolling::setOutwardNormal (PureRolling.cpp:19-47) as written: osot_pure_rolling_s33 (include/osot_mi355x.h)
+inline int kin_pure_rolling_s33(const double* nrm, double* s33, double* unit) {
+    if (!nrm || !s33) return OSOT_ERR_INVALID;
+    const double len = std::sqrt(nrm[0] * nrm[0] + nrm[1] * nrm[1] + nrm[2] * nrm[2]);
+    if (!(len > 0.0) || !(len <= 1.0e300)) return OSOT_ERR_INVALID;
+    const double uz[3] = {nrm[0] / len, nrm[1] / len, nrm[2] / len};
+    int x = 0;                                              // ux = e1
+    if (std::fabs(uz[1]) < std::fabs(uz[x])) x = 1;         // e2 against e1
+    if (std::fabs(uz[2]) < std::fabs(uz[x])) x = 2;         // e3 against the ux chosen so far
+    double ux[3] = {0.0, 0.0, 0.0};
+    ux[x] = 1.0;
+    const double uy[3] = {uz[1] * ux[2] - uz[2] * ux[1], uz[2] * ux[0] - uz[0] * ux[2], uz[0] * ux[1] - uz[1] * ux[0]};
+    for (int i = 0; i < 3; ++i) { s33[3 * i] = ux[i]; s33[3 * i + 1] = uy[i]; s33[3 * i + 2] = uz[i]; }   // columns ux, uy, uz
+    if (unit) for (int i = 0; i < 3; ++i) unit[i] = uz[i];
     return OSOT_OK;
 }
 
@@ -250,6 +294,118 @@ __device__ inline __attribute__((noinline)) void kin_convex_pair(const DevKin* _
 #pragma unroll
     for (int i = 0; i < 3; ++i) { ca[i] = r.ca[i]; cb[i] = r.cb[i]; }
 }
+// cross3 for the functions below that are written without contraction (the pragma is lexical: an inlined cross3 keeps its own setting)
+__device__ __forceinline__ void cross3_as_written(const double* a, const double* b, double* o) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+// ---- row sets (osot_kin_desc.rowset_*): the rows of ONE set, lane = joint.  colw: the lane's column of the frame's WORLD Jacobian
+// [linear; angular] (zero for a lane without a joint), Rf: the frame's world rotation; M(pose) is uniform over the lanes, the product
+// is lane-local; A / b / qd already point at the instance (A, b may be null).  The one cross-lane step is the split contact's
+// b = -sum_{j >= 6} A_j qdot_j (colsum: every lane calls it).  Written without contraction (the bits of the expressions as written,
+// in every instantiation and in the host build) and not inlined (one body per JMAX beside the producer's stages).
+template <int JMAX>
+__device__ inline __attribute__((noinline)) void kin_rowset(const DevKin* __restrict__ K, const int s, double* A, double* b, const double* qd,
+                                                            const bool live, const bool valid, const int j, const int n, const double* colw,
+                                                            const double* Rf) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const int kind = K->d.rowset_kind[s], mask = K->d.rowset_row_mask[s];
+    const bool split = K->d.rowset_split[s] != 0;
+    const double* P = K->d.rowset_param[s];
+    double row[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    if (kind == OSOT_ROWSET_CONTACT) {
+        // A = K Ad(R_f') J_f (velocity/Contact.cpp:19-33)
+        double v[6];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            v[i] = Rf[i] * colw[0] + Rf[3 + i] * colw[1] + Rf[6 + i] * colw[2];
+            v[3 + i] = Rf[i] * colw[3] + Rf[3 + i] * colw[4] + Rf[6 + i] * colw[5];
+        }
+#pragma unroll
+        for (int r = 0; r < 6; ++r)
+            row[r] = P[6 * r] * v[0] + P[6 * r + 1] * v[1] + P[6 * r + 2] * v[2] + P[6 * r + 3] * v[3] + P[6 * r + 4] * v[4] + P[6 * r + 5] * v[5];
+    } else if (kind == OSOT_ROWSET_PURE_ROLLING) {
+        // A = S [J_lin + J_ang x d; J_ang], d = -r n, S = [S33 0; 0 0 0 a'], a = (R_f e_z) x n normalised (PureRolling.cpp:50-77)
+        const double d[3] = {-1.0 * P[0] * P[1], -1.0 * P[0] * P[2], -1.0 * P[0] * P[3]};
+        double cx[3], a[3];
+        cross3_as_written(colw + 3, d, cx);
+        const double jc[3] = {colw[0] + cx[0], colw[1] + cx[1], colw[2] + cx[2]};
+#pragma unroll
+        for (int i = 0; i < 3; ++i) row[i] = P[4 + 3 * i] * jc[0] + P[4 + 3 * i + 1] * jc[1] + P[4 + 3 * i + 2] * jc[2];
+        const double ez[3] = {Rf[2], Rf[5], Rf[8]};
+        cross3_as_written(ez, P + 1, a);
+        const double an = sqrt(a[0] * a[0] + a[1] * a[1] + a[2] * a[2]);      // (0 for a wheel axis along n: no guard, as the reference)
+        a[0] /= an; a[1] /= an; a[2] /= an;
+        row[3] = a[0] * colw[3] + a[1] * colw[4] + a[2] * colw[5];
+    } else {
+        // OmniWheels4X.cpp:22-74: the constant selection in columns 0 .. 5, R_base (r / 4) v_j behind them
+        if (j < 6) {
+            row[0] = (j == 0) ? 1.0 : 0.0; row[1] = (j == 1) ? 1.0 : 0.0; row[2] = (j == 5) ? 1.0 : 0.0;
+        } else {
+            const double il = 1.0 / (P[0] + P[1]), q4 = P[2] / 4.0;
+            double v[3] = {0.0, 0.0, 0.0};
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                if (K->d.rowset_wheel[s][w] != j) continue;
+                v[0] -= 1.0;
+                v[1] -= (w == 0 || w == 3) ? -1.0 : 1.0;
+                v[2] -= (w == 0 || w == 2) ? -il : il;
+            }
+#pragma unroll
+            for (int i = 0; i < 3; ++i) v[i] *= q4;
+#pragma unroll
+            for (int i = 0; i < 3; ++i) row[i] = Rf[3 * i] * v[0] + Rf[3 * i + 1] * v[1] + Rf[3 * i + 2] * v[2];
+        }
+    }
+    const int nrows = kin_rowset_rows(kind);
+    const double qj = (split && b && qd) ? qd[j < n ? j : 0] : 0.0;
+    int o = 0;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        if (r >= nrows || !((mask >> r) & 1)) continue;
+        if (split) {
+            if (A && valid && live && j < 6) A[o * 6 + j] = row[r];
+            if (b) {
+                const double sum = colsum<JMAX>((valid && j >= 6) ? row[r] * qj : 0.0);
+                if (j == 0 && live) b[o] = -sum;
+            }
+        } else if (A && valid && live) {
+            A[o * n + j] = row[r];
+        }
+        ++o;
+    }
+}
+// ---- gaze reference of ONE gaze (Gaze.cpp:52-74, cartesian_utils.cpp:27-35), one lane: T = [R | p] the pose its frame publishes,
+// gp the point, ref the 12 doubles of the Cartesian leaf's reference pose -- overwritten where |t| >= 0.2, untouched below.
+__device__ inline __attribute__((noinline)) void kin_gaze_ref(const double* T, const double* gp, double* ref) {
+#ifdef __clang__
+#pragma clang fp contract(off)
+#endif
+    const double dg[3] = {gp[0] - T[9], gp[1] - T[10], gp[2] - T[11]};
+    double t[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) t[i] = T[i] * dg[0] + T[3 + i] * dg[1] + T[6 + i] * dg[2];      // R'(g - p)
+    const double nt = sqrt(t[0] * t[0] + t[1] * t[1] + t[2] * t[2]);
+    if (!(nt >= 0.2)) return;                                                                 // GAZE_THRESHOLD
+    // pan = atan2(t_y, t_x), tilt = atan2(t_z, rho) with rho = sqrt(t_y^2 + t_x^2): their cosines and sines are ratios of t, rho and
+    // |t| -- formed directly, without the round trip through the angles (square roots and divisions are correctly rounded on the host
+    // and on the device alike; atan2 / sincos are not, and cost a few hundred instructions).  rho = 0: pan = atan2(0, 0) = 0.
+    const double rho = sqrt(t[1] * t[1] + t[0] * t[0]);
+    const bool has_pan = rho > 0.0;
+    const double cp = has_pan ? t[0] / rho : 1.0, sp = has_pan ? t[1] / rho : 0.0;
+    const double cs = rho / nt, sn = -(t[2] / nt);                                            // cos(-tilt), sin(-tilt)
+    // Identity, DoRotZ(pan), DoRotY(-tilt): [[cp cs, -sp, cp sn], [sp cs, cp, sp sn], [-sn, 0, cs]]
+    ref[0] = cs * cp; ref[1] = -sp; ref[2] = sn * cp;
+    ref[3] = cs * sp; ref[4] = cp;  ref[5] = sn * sp;
+    ref[6] = -sn;     ref[7] = 0.0; ref[8] = cs;
+    ref[9] = 0.0; ref[10] = 0.0; ref[11] = 0.0;
+}
 // LDS one instance of kin_instance needs, in doubles (the int / 64-bit tables included): transforms, axes, centres of mass, parents,
 // ancestor masks -- and the pair table of the PAIRS instantiation
 template <int JMAX> constexpr int kin_lds_doubles(bool pairs) {
@@ -260,13 +416,15 @@ template <int JMAX> constexpr int kin_lds_doubles(bool pairs) {
 // per wavefront (JMAX = 64) or two (JMAX = 32: the halves); osot_control_cycle_kernel calls it in front of the instance's update.
 // PAIRS: the instantiation with the self-collision stage (step 5); the other one keeps the leaner register / LDS budget
 // CONVEX (with PAIRS): the stage also serves pairs of convex shapes (kin_convex_pair); launched only for a model that has one
+// ROWS: the instantiation with the row sets and gaze references (kin_rowset, kin_gaze_ref); launched only for a call that binds one.
+// Off, every line of it is behind `if constexpr`: the other instantiations are the code they were
 // developer knob (tools/build_variant.sh NAME -DOSOT_KIN_PHASES): instance 0 prints the clock count of every stage
 #ifdef OSOT_KIN_PHASES
 #define KIN_PHASE(tag) do { const long long t_ = (long long)clock64(); if (inst == 0 && j == 0) printf("KIN " tag " %lld\n", t_ - kph_); kph_ = (long long)clock64(); } while (0)
 #else
 #define KIN_PHASE(tag) do { } while (0)
 #endif
-template <bool PAIRS, int JMAX, bool CONVEX = false>
+template <bool PAIRS, int JMAX, bool CONVEX = false, bool ROWS = false>
 __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const osot_kin_batch& Bt, const long long inst, const bool live,
                                              const int j, double* lds) {
     constexpr int TS = OSOT_KIN_TS;
@@ -447,6 +605,37 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
                 pose_out[inst * 12 + 9 + r] = Rb[r] * dp[0] + Rb[3 + r] * dp[1] + Rb[6 + r] * dp[2];
             }
         }
+        if constexpr (ROWS) {
+            // gaze references, lane = frame: the pose the frame publishes (the expressions above), whether or not it is bound
+            const int ng = K->d.n_gaze;
+            if (ng > 0 && j < nfr && live) {
+                double T[12];
+                if (base_f <= 0) {
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) T[i] = Rf[i];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) T[9 + i] = pj[i] + t[i];
+                } else {
+                    const double* Bw = Fw + (base_f - 1) * 14;
+                    double Rb[9], dp[3];
+#pragma unroll
+                    for (int i = 0; i < 9; ++i) Rb[i] = Bw[i];
+#pragma unroll
+                    for (int i = 0; i < 3; ++i) dp[i] = (pj[i] + t[i]) - Bw[9 + i];
+#pragma unroll
+                    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+                        for (int cc = 0; cc < 3; ++cc) T[3 * r + cc] = Rb[r] * Rf[cc] + Rb[3 + r] * Rf[3 + cc] + Rb[6 + r] * Rf[6 + cc];
+                        T[9 + r] = Rb[r] * dp[0] + Rb[3 + r] * dp[1] + Rb[6 + r] * dp[2];
+                    }
+                }
+                for (int g = 0; g < ng; ++g) {
+                    const double* gp = Bt.gaze_point[g];
+                    double* gr = Bt.gaze_ref[g];
+                    if (gp && gr && K->d.gaze_frame[g] == j) kin_gaze_ref(T, gp + inst * 3, gr + inst * 12);
+                }
+            }
+        }
     }
     // ---- 3b. contact points (the world transforms in LDS are unchanged since the barrier of 3a)
     if (Bt.points && K->d.n_points > 0 && live) kin_points(K, Bt.points, inst, j, Tw);
@@ -468,8 +657,10 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
         const int jb = (bf >= 0) ? (int)Fw[bf * 14 + 12] : 0;
         const unsigned long long cm = Fq[f];
         double* Jf = Bt.frame_J[f];                      // (the argument struct: scalar loads, a uniform base address for the stores)
-        if (!Jf) continue;
+        if constexpr (!ROWS) { if (!Jf) continue; }
+        else { if (!Jf && !((K->rowset_frames >> f) & 1u)) continue; }
         const long long jstride = Bt.frame_J_stride[f];
+        [[maybe_unused]] double colw[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};      // ROWS: the world column, in front of the frame's options
         if (valid) {
             double col[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
             // joint j moves the distal link (+1), the base link (-1: the base body's point at the distal origin moves the same way,
@@ -489,6 +680,10 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
                     for (int i = 0; i < 6; ++i) col[i] = -col[i];
                 }
             }
+            if constexpr (ROWS) {
+#pragma unroll
+                for (int i = 0; i < 6; ++i) colw[i] = col[i];
+            }
             if (body || bf >= 0) {
                 // BODY Jacobian Ad(R_f') J (Cartesian.cpp:93-100): both halves rotated by R_f'; a relative Jacobian is expressed in
                 // its base frame: R_b' (getRelativeJacobian, Cartesian.cpp:75-76) -- and BODY on top of that is Ad((R_b'R_d)') R_b' = R_d'
@@ -505,9 +700,26 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
                 for (int i = 0; i < 3; ++i) { col[i] = rl[i]; col[3 + i] = ra[i]; }
             }
             const bool masked = cm != 0ull && !((cm >> j) & 1ull);
-            double* J = Jf + inst * jstride;
+            if (!ROWS || Jf) {
+                double* J = Jf + inst * jstride;
 #pragma unroll
-            for (int r = 0; r < 6; ++r) J[r * n + j] = masked ? 0.0 : col[r];
+                for (int r = 0; r < 6; ++r) J[r * n + j] = masked ? 0.0 : col[r];
+            }
+        }
+        if constexpr (ROWS) {
+            // the row sets on this frame (a frame with one has the world as its base: colw is its world column)
+            if ((K->rowset_frames >> f) & 1u) {
+                const int ns = K->d.n_rowsets;
+                for (int s = 0; s < ns; ++s) {
+                    if (K->d.rowset_frame[s] != f) continue;
+                    double* As = Bt.rowset_A[s];
+                    double* bs = Bt.rowset_b[s];
+                    if (!As && !bs) continue;
+                    const long long io = live ? inst : 0;
+                    kin_rowset<JMAX>(K, s, As ? As + io * Bt.rowset_A_stride[s] : nullptr, bs ? bs + io * Bt.rowset_b_stride[s] : nullptr,
+                                     Bt.rowset_qdot ? Bt.rowset_qdot + io * n : nullptr, live, valid, j, n, colw, Rf);
+                }
+            }
         }
     }
     KIN_PHASE("frames");
@@ -687,7 +899,7 @@ __device__ __forceinline__ void kin_instance(const DevKin* __restrict__ K, const
 
 // JMAX = 32: TWO instances per wavefront (lanes 0..31 and 32..63 each run a robot of <= 32 joints: every instruction, every
 // 64-lane store carries two instances);  JMAX = 64: one instance per wavefront.
-template <bool PAIRS, int JMAX, bool CONVEX = false>
+template <bool PAIRS, int JMAX, bool CONVEX = false, bool ROWS = false>
 __global__ void __launch_bounds__(64) osot_kin_kernel(const DevKin* __restrict__ K, const osot_kin_batch Bt) {
     constexpr int PACK = 64 / JMAX;
     constexpr int SLICE = kin_lds_doubles<JMAX>(PAIRS);
@@ -696,7 +908,7 @@ __global__ void __launch_bounds__(64) osot_kin_kernel(const DevKin* __restrict__
     const int j = (PACK == 2) ? (int)(threadIdx.x & 31u) : (int)threadIdx.x;
     const long long inst = (long long)blockIdx.x * PACK + sub;
     const bool live = inst < Bt.B;            // (an odd batch leaves the last wavefront's second half idle)
-    kin_instance<PAIRS, JMAX, CONVEX>(K, Bt, inst, live, j, kin_lds + sub * SLICE);
+    kin_instance<PAIRS, JMAX, CONVEX, ROWS>(K, Bt, inst, live, j, kin_lds + sub * SLICE);
 }
 
 }  // namespace osot

@@ -201,10 +201,12 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
         OSOT_F(pair_radius) OSOT_F(frame_body) OSOT_F(frame_col_mask) OSOT_F(com_col_mask) OSOT_F(pair_kind) OSOT_F(pair_env)
         OSOT_F(pair_box) OSOT_F(pair_shape_R) OSOT_F(pair_shape_p) OSOT_F(n_env) OSOT_F(frame_base)
         OSOT_F(pair_kind_a) OSOT_F(pair_size_a) OSOT_F(pair_shape_R_a) OSOT_F(pair_shape_p_a) OSOT_F(pair_hull) OSOT_F(n_hull_vertices)
-        OSOT_F(hull_vertex) OSOT_F(n_points) OSOT_F(point_joint) OSOT_F(point_p) OSOT_LAYOUT_END()
+        OSOT_F(hull_vertex) OSOT_F(n_rowsets) OSOT_F(rowset_kind) OSOT_F(rowset_frame) OSOT_F(rowset_row_mask) OSOT_F(rowset_split)
+        OSOT_F(rowset_wheel) OSOT_F(rowset_param) OSOT_F(n_gaze) OSOT_F(gaze_frame) OSOT_F(n_points) OSOT_F(point_joint) OSOT_F(point_p) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_kin_batch) OSOT_F(B) OSOT_F(q) OSOT_F(frame_pose) OSOT_F(frame_J) OSOT_F(frame_J_stride) OSOT_F(com)
         OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(pair_dist) OSOT_F(pair_J) OSOT_F(pair_J_stride) OSOT_F(env_pose) OSOT_F(env_pose_stride)
-        OSOT_F(pair_points) OSOT_F(points) OSOT_LAYOUT_END()
+        OSOT_F(pair_points) OSOT_F(rowset_A) OSOT_F(rowset_A_stride) OSOT_F(rowset_b) OSOT_F(rowset_b_stride)
+        OSOT_F(rowset_qdot) OSOT_F(gaze_point) OSOT_F(gaze_ref) OSOT_F(points) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_shape) OSOT_F(kind) OSOT_F(size) OSOT_F(radius) OSOT_F(n_vertices) OSOT_F(vertices) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_desc) OSOT_F(inertia) OSOT_F(gravity) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_dyn_batch) OSOT_F(B) OSOT_F(q) OSOT_F(qdot) OSOT_F(M) OSOT_F(M_stride) OSOT_F(h) OSOT_F(frame_Jdot_qdot)
@@ -1140,6 +1142,7 @@ int osot_backend_get_num_constraints(osot_backend* be, int* nc) {
 struct osot_kin {
     DevKin* dev;
     int n, n_frames, n_pairs, n_env, device;
+    int n_rowsets, n_gaze, n_split;      // row sets, gaze references, split contact row sets (osot_kin_desc.rowset_*, gaze_*)
     int n_convex;      // pairs that are not capsule / capsule or capsule / box: served by the CONVEX instantiation of the producer alone
 };
 
@@ -1186,6 +1189,11 @@ int osot_kin_create(const osot_kin_desc* d, int device, osot_kin** out) {
         const int rc = kin_check_points(d, &why);
         if (rc != OSOT_OK) return fail(rc, why);
     }
+    {
+        const char* why = "";
+        const int rc = kin_check_rowsets(d, &why);
+        if (rc != OSOT_OK) return fail(rc, why);
+    }
     if (d->n_hull_vertices < 0 || d->n_hull_vertices > OSOT_KIN_MAX_HULL_VERTICES) return fail(OSOT_ERR_INVALID, "hull vertex count out of range (0..256)");
     for (int v = 0; v < d->n_hull_vertices; ++v)
         for (int i = 0; i < 3; ++i)
@@ -1220,6 +1228,8 @@ int osot_kin_create(const osot_kin_desc* d, int device, osot_kin** out) {
     osot_kin* k = new osot_kin();
     k->n = d->n; k->n_frames = d->n_frames; k->n_pairs = d->n_pairs; k->n_env = d->n_env; k->device = device;
     k->n_convex = n_convex;
+    k->n_rowsets = d->n_rowsets; k->n_gaze = d->n_gaze; k->n_split = 0;
+    for (int s = 0; s < d->n_rowsets; ++s) k->n_split |= d->rowset_split[s] ? (1 << s) : 0;
     hipError_t e = hipMalloc(&k->dev, sizeof(DevKin));
     if (e == hipSuccess) e = hipMemcpy(k->dev, &h, sizeof(DevKin), hipMemcpyHostToDevice);
     if (e != hipSuccess) { delete k; return fail(OSOT_ERR_HIP, hipGetErrorString(e)); }
@@ -1245,10 +1255,39 @@ int osot_kinematics(osot_kin* k, const osot_kin_batch* b, void* hip_stream) {
     const bool pairs = k->n_pairs > 0 && (b->pair_dist || b->pair_J || b->pair_points);
     if (pairs && k->n_env > 0 && !b->env_pose) return fail(OSOT_ERR_INVALID, "the model has environment shapes but env_pose is null");
     const bool convex = pairs && k->n_convex > 0;      // the instantiation with the per-lane GJK: only where a pair needs it
+    // row sets and gaze references: their own instantiation, only where the call binds one
+    bool rows = false;
+    for (int s = 0; s < OSOT_KIN_MAX_ROWSETS; ++s) {
+        const bool bound_b = b->rowset_b[s] != nullptr;
+        if (s >= k->n_rowsets) {
+            if (b->rowset_A[s] || bound_b) return fail(OSOT_ERR_INVALID, "a row set output is bound beyond the model's n_rowsets");
+            continue;
+        }
+        if (bound_b && !((k->n_split >> s) & 1)) return fail(OSOT_ERR_INVALID, "rowset_b is the output of a split contact row set only");
+        if (bound_b && !b->rowset_qdot) return fail(OSOT_ERR_INVALID, "rowset_b is bound but rowset_qdot is null");
+        if (bound_b && b->rowset_b_stride[s] < 1) return fail(OSOT_ERR_INVALID, "rowset_b is bound without a stride");
+        rows = rows || b->rowset_A[s] || bound_b;
+    }
+    for (int g = 0; g < OSOT_KIN_MAX_FRAMES; ++g) {
+        if (!b->gaze_ref[g] && !b->gaze_point[g]) continue;
+        if (g >= k->n_gaze) return fail(OSOT_ERR_INVALID, "a gaze buffer is bound beyond the model's n_gaze");
+        if (!b->gaze_ref[g] || !b->gaze_point[g]) return fail(OSOT_ERR_INVALID, "a gaze needs both gaze_point and gaze_ref");
+        rows = true;
+    }
+    if (rows && convex)
+        return fail(OSOT_ERR_UNSUPPORTED, "row sets / gaze references with convex collision pairs: two osot_kinematics calls (pair outputs in one, row sets in the other)");
     const dim3 grid((unsigned)(k->n <= 32 ? (b->B + 1) / 2 : b->B)), block(64);   // <= 32 joints: two instances per wavefront
     hipStream_t st = (hipStream_t)hip_stream;
     const DevKin* dk = (const DevKin*)k->dev;
-    if (k->n <= 32) {
+    if (rows) {
+        if (k->n <= 32) {
+            if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 32, false, true>), grid, block, 0, st, dk, *b);
+            else hipLaunchKernelGGL((osot_kin_kernel<false, 32, false, true>), grid, block, 0, st, dk, *b);
+        } else {
+            if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 64, false, true>), grid, block, 0, st, dk, *b);
+            else hipLaunchKernelGGL((osot_kin_kernel<false, 64, false, true>), grid, block, 0, st, dk, *b);
+        }
+    } else if (k->n <= 32) {
         if (convex) hipLaunchKernelGGL((osot_kin_kernel<true, 32, true>), grid, block, 0, st, dk, *b);
         else if (pairs) hipLaunchKernelGGL((osot_kin_kernel<true, 32>), grid, block, 0, st, dk, *b);
         else hipLaunchKernelGGL((osot_kin_kernel<false, 32>), grid, block, 0, st, dk, *b);
@@ -1258,6 +1297,11 @@ int osot_kinematics(osot_kin* k, const osot_kin_batch* b, void* hip_stream) {
         else hipLaunchKernelGGL((osot_kin_kernel<false, 64>), grid, block, 0, st, dk, *b);
     }
     HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+int osot_pure_rolling_s33(const double* normal, double* s33, double* normal_unit) {
+    if (kin_pure_rolling_s33(normal, s33, normal_unit) != OSOT_OK) return fail(OSOT_ERR_INVALID, "pure rolling: a null or zero outward normal");
     return OSOT_OK;
 }
 
@@ -1427,6 +1471,8 @@ static int control_launch(osot_solver* s, osot_kin* k, const osot_kin_batch* kb,
     // (the fused kernels carry the closed-form pair stage only: no instantiation of theirs runs GJK)
     if (k->n_convex > 0 && (kb->pair_dist || kb->pair_J || kb->pair_points))
         return fail(OSOT_ERR_UNSUPPORTED, "convex collision pairs: use osot_kinematics + osot_cycle");
+    if (k->n_rowsets > 0 || k->n_gaze > 0)
+        return fail(OSOT_ERR_UNSUPPORTED, "row sets / gaze references: use osot_kinematics + osot_cycle");
     DevUpdate U;
     const char* why = "";
     int rc = make_update_args(s->plan, s->h_uplan, leaf, out, s->d_uplan, U, &why);

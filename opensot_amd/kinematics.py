@@ -49,6 +49,65 @@ class KinModel:
     # contact points (velocity::ConvexHull's links in contact): (joint index, p[3] in that joint's link frame); their world positions
     # are the producer's `points` output, the OSOT_ROWS_CONVEX_HULL leaf p2
     points: list = field(default_factory=list)
+    # row sets (osot_kin_desc.rowset_*): dicts(kind, frame, mask, split, wheels, param[36]) -- add_contact_rows, add_pure_rolling,
+    # add_omni_wheels_4x; gaze references: frame indices -- add_gaze
+    rowsets: list = field(default_factory=list)
+    gazes: list = field(default_factory=list)
+
+    def _frame(self, frame):
+        f = self.frame_index(frame) if isinstance(frame, str) else int(frame)
+        if not 0 <= f < len(self.frames):
+            raise ValueError(f"frame {frame!r} is not in the model")
+        return f
+
+    def _add_rowset(self, kind, frame, mask, param, split=False, wheels=(0, 0, 0, 0)):
+        if len(self.rowsets) >= abi.KIN_MAX_ROWSETS:
+            raise ValueError(f"the producer holds {abi.KIN_MAX_ROWSETS} row sets")
+        P = np.zeros(36)
+        P[:len(param)] = param
+        self.rowsets.append(dict(kind=kind, frame=self._frame(frame), mask=int(mask), split=bool(split), wheels=tuple(int(w) for w in wheels),
+                                 param=P))
+        return len(self.rowsets) - 1
+
+    def rowset_rows(self, s):
+        """rows row set s writes (the bits of its row mask)"""
+        return bin(self.rowsets[s]["mask"]).count("1")
+
+    def add_contact_rows(self, frame, K, split=False):
+        """tasks::velocity::Contact (Contact.cpp:19-33): rows K Ad(R_f') J_f, K [rows][6] with rows <= 6; split=True:
+        tasks::floating_base::Contact (floating_base/Contact.cpp:47-67, lambda = 0): the first six columns as A of a 6-variable plan and
+        b = -A[:, 6:] qdot[6:] -> the row set's index"""
+        K = np.atleast_2d(np.asarray(K, dtype=float))
+        if K.shape[1] != 6 or not 1 <= K.shape[0] <= 6:
+            raise ValueError("K is rows x 6 with 1 .. 6 rows")
+        P = np.zeros((6, 6))
+        P[:K.shape[0]] = K
+        return self._add_rowset(abi.ROWSET_CONTACT, frame, (1 << K.shape[0]) - 1, P.reshape(36), split=split)
+
+    def add_pure_rolling(self, frame, radius, normal=(0, 0, 1), rows=(0, 1, 2, 3)):
+        """tasks::velocity::PureRolling on a wheel frame that spins about its local z (PureRolling.cpp:50-77); rows (0, 1) or (0, 1, 2):
+        PureRollingPosition, (3,): PureRollingOrientation -> the row set's index"""
+        nrm = (C.c_double * 3)(*[float(v) for v in normal])
+        s33, unit = (C.c_double * 9)(), (C.c_double * 3)()
+        abi.check(abi.lib().osot_pure_rolling_s33(nrm, s33, unit), "osot_pure_rolling_s33")
+        if not rows or any(not 0 <= int(r) < 4 for r in rows):
+            raise ValueError("pure rolling has the rows 0 .. 3")
+        return self._add_rowset(abi.ROWSET_PURE_ROLLING, frame, sum(1 << int(r) for r in set(rows)), [float(radius)] + list(unit) + list(s33))
+
+    def add_omni_wheels_4x(self, base_frame, l1, l2, r, wheels):
+        """constraints::velocity::OmniWheels4X (OmniWheels4X.cpp:22-74): 3 rows; wheels: the joints (index or name) of the front-left,
+        front-right, hind-left and hind-right wheels -> the row set's index"""
+        if len(wheels) != 4:
+            raise ValueError("joint_wheels_name != 4")
+        w = [self.names.index(x) if isinstance(x, str) else int(x) for x in wheels]
+        return self._add_rowset(abi.ROWSET_OMNI4X, base_frame, 7, [float(l1), float(l2), float(r)], wheels=w)
+
+    def add_gaze(self, frame):
+        """tasks::velocity::Gaze's reference update on a frame (Gaze.cpp:52-74) -> the gaze's index"""
+        if len(self.gazes) >= abi.KIN_MAX_FRAMES:
+            raise ValueError(f"the producer holds {abi.KIN_MAX_FRAMES} gaze references")
+        self.gazes.append(self._frame(frame))
+        return len(self.gazes) - 1
 
     def add_point(self, link_or_joint, p=(0.0, 0.0, 0.0)):
         """a contact point fixed at p in the frame of a joint's link (joint index or name) -> its index"""
@@ -252,6 +311,17 @@ class KinModel:
             d.point_joint[i] = int(j)
             for c in range(3):
                 d.point_p[i][c] = float(p[c])
+        d.n_rowsets = len(self.rowsets)
+        for k, rs in enumerate(self.rowsets):
+            d.rowset_kind[k], d.rowset_frame[k], d.rowset_row_mask[k] = rs["kind"], rs["frame"], rs["mask"]
+            d.rowset_split[k] = 1 if rs["split"] else 0
+            for i in range(4):
+                d.rowset_wheel[k][i] = rs["wheels"][i]
+            for i in range(36):
+                d.rowset_param[k][i] = float(rs["param"][i])
+        d.n_gaze = len(self.gazes)
+        for g, f in enumerate(self.gazes):
+            d.gaze_frame[g] = f
         d.n_pairs = len(self.pairs)
         d.n_env = sum(1 for e in self.env_shapes if e["link"] == "world")
         hulls = {}      # vertex bytes -> first vertex: a hull that several pairs share is stored once
@@ -423,22 +493,25 @@ class Kinematics:
             pass
 
     def forward(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None,
-                batch=None, pair_points=None):
+                batch=None, pair_points=None, rowset_A=None, rowset_b=None, qdot=None, gaze_point=None, gaze_ref=None):
         """osot_kinematics for the batch `batch_args` describes, stream-ordered on torch's current stream (batch: a batch_args()
         result to reuse)"""
         kb = batch if batch is not None else self.batch_args(q, frame_pose, frame_J, com, com_J, pair_dist, pair_J, env_pose, points,
-                                                                      pair_points)
+                                                                      pair_points, rowset_A, rowset_b, qdot, gaze_point, gaze_ref)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         abi.check(self._lib.osot_kinematics(self._h, C.byref(kb), stream), "osot_kinematics")
 
     def batch_args(self, q, frame_pose=None, frame_J=None, com=None, com_J=None, pair_dist=None, pair_J=None, env_pose=None, points=None,
-                   pair_points=None):
+                   pair_points=None, rowset_A=None, rowset_b=None, qdot=None, gaze_point=None, gaze_ref=None):
         """the osot_kin_batch of a call (pointers and strides only; the tensors must outlive its use).  q [B][n] (device).  frame_pose: {frame index: tensor [B][12]}; frame_J: {frame index: (A_k tensor [B][ma][n],
         first row)}; com: tensor [B][3]; com_J: (A_k tensor, first row).
         env_pose: poses of the environment shapes, a device tensor [n_env][12] (one world for all instances) or
         [B][n_env][12]; default: the model's own (add_collision_shape / move_collision_shape), uploaded when they change.
         points: tensor [B][n_points][3], the world positions of the model's contact points (add_point)
-        pair_points: tensor [B][n_pairs][6], the witness points ca, cb of every pair (world, on the cores)"""
+        pair_points: tensor [B][n_pairs][6], the witness points ca, cb of every pair (world, on the cores)
+        rowset_A: {row set index: (A_k or C tensor [B][rows][n] -- [B][rows][6] for a split contact --, first row)}; rowset_b: {row set
+        index: (b tensor [B][rows], first entry)} with qdot [B][n], for the split contacts; gaze_point: {gaze index: tensor [B][3]},
+        gaze_ref: {gaze index: tensor [B][12]}, overwritten where the point is at least 0.2 away"""
         B, n = q.shape
         assert n == self.model.n and q.is_contiguous()
         kb = abi.KinBatch()
@@ -474,6 +547,26 @@ class Kinematics:
             assert pair_points.is_contiguous() and pair_points.dtype == torch.float64 and pair_points.shape[0] >= B
             assert tuple(pair_points.shape[1:]) == (len(self.model.pairs), 6)
             kb.pair_points = pair_points.data_ptr()
+        for s, (A, row) in (rowset_A or {}).items():
+            cols = 6 if self.model.rowsets[s]["split"] else n
+            assert A.is_contiguous() and A.dtype == torch.float64 and A.shape[0] >= B and A.shape[2] == cols
+            assert 0 <= row and row + self.model.rowset_rows(s) <= A.shape[1]
+            kb.rowset_A[s] = A.data_ptr() + 8 * row * cols
+            kb.rowset_A_stride[s] = A.shape[1] * cols
+        for s, (bt, first) in (rowset_b or {}).items():
+            assert bt.is_contiguous() and bt.dtype == torch.float64 and bt.shape[0] >= B
+            assert 0 <= first and first + self.model.rowset_rows(s) <= bt.shape[1]
+            kb.rowset_b[s] = bt.data_ptr() + 8 * first
+            kb.rowset_b_stride[s] = bt.shape[1]
+        if qdot is not None:
+            assert qdot.is_contiguous() and qdot.dtype == torch.float64 and tuple(qdot.shape) == (B, n)
+            kb.rowset_qdot = qdot.data_ptr()
+        for g, t in (gaze_point or {}).items():
+            assert t.is_contiguous() and t.dtype == torch.float64 and t.shape[0] >= B and t.shape[1] == 3
+            kb.gaze_point[g] = t.data_ptr()
+        for g, t in (gaze_ref or {}).items():
+            assert t.is_contiguous() and t.dtype == torch.float64 and t.shape[0] >= B and t.shape[1] == 12
+            kb.gaze_ref[g] = t.data_ptr()
         n_env = sum(1 for e in self.model.env_shapes if e["link"] == "world")
         if n_env and (pair_dist is not None or pair_J is not None or pair_points is not None):
             if env_pose is None:

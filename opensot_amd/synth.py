@@ -1216,3 +1216,196 @@ def make_coman_id_momentum_stack(B, seed=None, tree=None, inertia=None, eps_fact
     leaf["task"] = [leaf["task"][0], [(np.zeros((B, 3)), None, None)], leaf["task"][1]]
     leaf["state"]["momentum"] = dict(level=1, row=0, lam=1.0, K=np.eye(3))
     return plan, leaf, model
+
+
+# ---- wheeled-legged robots: PureRolling / Contact / OmniWheels4X rows from the kinematics producer --------------------------------
+WHEEL_RADIUS = 0.08
+
+
+def make_wheeled_tree(legs=4, leg_joints=2):
+    """A wheeled-legged tree: a floating base of 3 prismatic + 3 revolute coordinates (x, y, z, roll, pitch, yaw), then per leg
+    `leg_joints` revolute joints (a hip yaw about z, pitch joints about y) and a wheel joint spinning about its LOCAL z, which lies
+    along the base's y at q = 0 (the convention of PureRolling: _wheel_axis = (0, 0, 1), PureRolling.cpp:10).  Legs in the order
+    front-left, front-right, hind-left, hind-right (OmniWheels4X's order).  Frames: "base" on the last base joint, "wheel_<i>" at the
+    centre of wheel i.  n = 6 + legs * (leg_joints + 1) <= 64."""
+    from . import kinematics as kin
+    P, R = abi.JOINT_PRISMATIC, abi.JOINT_REVOLUTE
+    X, Y, Z = [1.0, 0, 0], [0, 1.0, 0], [0, 0, 1.0]
+    I = np.eye(3)
+    Rw = np.array([[1.0, 0, 0], [0, 0, 1.0], [0, -1.0, 0]])        # the wheel joint's frame: its z is the parent's y
+    rows = [("base_x", -1, P, X, (0, 0, 0), I, 0.0), ("base_y", 0, P, Y, (0, 0, 0), I, 0.0), ("base_z", 1, P, Z, (0, 0, 0), I, 0.0),
+            ("base_roll", 2, R, X, (0, 0, 0), I, 0.0), ("base_pitch", 3, R, Y, (0, 0, 0), I, 0.0), ("base_yaw", 4, R, Z, (0, 0, 0), I, 20.0)]
+    assert legs >= 1 and leg_joints >= 1 and 6 + legs * (leg_joints + 1) <= abi.KIN_MAX_JOINTS
+    wheels = []
+    for leg in range(legs):
+        sx, sy = (1.0 if (leg // 2) % 2 == 0 else -1.0), (1.0 if leg % 2 == 0 else -1.0)
+        parent = 5
+        for k in range(leg_joints):
+            xyz = (sx * 0.3, sy * 0.2, -0.05) if k == 0 else (0.05 * sx if k == 1 else 0.0, 0.0, -0.25)
+            rows.append((f"leg{leg}_j{k}", parent, R, Z if k == 0 else Y, xyz, I, 1.5))
+            parent = len(rows) - 1
+        rows.append((f"wheel_{leg}_joint", parent, R, Z, (0.0, sy * 0.05, -0.25), Rw, 1.0))
+        wheels.append(len(rows) - 1)
+    n = len(rows)
+    m = kin.KinModel(parent=[r[1] for r in rows], jtype=[r[2] for r in rows], axis=np.array([r[3] for r in rows], dtype=float),
+                     R0=np.array([r[5] for r in rows], dtype=float), p0=np.array([r[4] for r in rows], dtype=float),
+                     mass=np.array([r[6] for r in rows], dtype=float), com=np.zeros((n, 3)), names=[r[0] for r in rows])
+    m.frames = [("base", 5, I, (0.0, 0.0, 0.0))] + [(f"wheel_{i}", w, I, (0.0, 0.0, 0.0)) for i, w in enumerate(wheels)]
+    m.wheel_joints = wheels
+    return m
+
+
+def wheeled_posture(model, B, seed=0):
+    """B standing postures of make_wheeled_tree: the base within 0.2 m / 0.15 rad of the origin, legs bent by 0.2 .. 0.6 rad, wheels
+    anywhere; the wheel axes stay well away from the vertical"""
+    rng = np.random.default_rng(31000 + seed)
+    n = model.n
+    q = np.zeros((B, n))
+    q[:, :3] = rng.uniform(-0.2, 0.2, (B, 3)); q[:, 2] += 0.2 * ((n - 6) // len(model.wheel_joints))
+    q[:, 3:6] = rng.uniform(-0.15, 0.15, (B, 3))
+    for j in range(6, n):
+        if j in model.wheel_joints:
+            q[:, j] = rng.uniform(-3.0, 3.0, B)
+        elif model.axis[j][2] == 1.0:
+            q[:, j] = rng.uniform(-0.3, 0.3, B)
+        else:
+            q[:, j] = rng.uniform(0.2, 0.6, B) * (1.0 if (j % 2) else -1.0)
+    return q
+
+
+def make_wheeled_stack(B, seed=None, legs=4, leg_joints=4, omni=False, eps_factor=1e6):
+    """The velocity stack of a wheeled-legged robot with every model quantity LEFT FOR THE KINEMATICS PRODUCER:
+
+    levels : 0 = one tasks::velocity::PureRolling per wheel (4 rows each, b = 0: OSOT_TASK_GENERIC blocks whose rows the producer writes
+             into A_0), 1 = velocity::Cartesian on the base (the producer writes its Jacobian into A_1 and its pose into the leaf),
+             2 = velocity::Postural
+    box    : joint limits, velocity limits
+    rows   : omni=True: constraints::velocity::OmniWheels4X as a global equality block (OSOT_ROWS_GENERIC, lo = up = 0, rows written
+             into C by the producer)
+
+    leg_joints = 4 (26 coordinates): the 16 rolling rows and the base's 6 leave the posture 4 directions; with fewer joints the last
+    level's equalities outnumber the variables.
+    Returns (plan, leaf, model); leaf["state"] = q0, q_ref, base_step.  bind_wheeled() wires the device tensors."""
+    rng = np.random.default_rng(32000 if seed is None else seed)
+    model = make_wheeled_tree(legs, leg_joints)
+    n = model.n
+    for i in range(legs):
+        model.add_pure_rolling(f"wheel_{i}", WHEEL_RADIUS)
+    if omni:
+        assert legs == 4
+        model.add_omni_wheels_4x("base", 0.3, 0.2, WHEEL_RADIUS, model.wheel_joints)
+    q0 = wheeled_posture(model, B, seed=0 if seed is None else seed)
+    q_ref = q0 + rng.uniform(-0.05, 0.05, (B, n))
+    # the base's reference pose: a small step ahead of where it stands (filled in from the producer's pose by the binder)
+    base_step = np.concatenate([rng.uniform(-0.01, 0.01, (B, 2)), rng.uniform(-0.003, 0.003, (B, 1))], axis=1)
+    z = lambda *sh: np.zeros(sh)
+    levels = [[Task(abi.TASK_GENERIC, 4, name=f"pure_rolling_{i}") for i in range(legs)],
+              [Task(abi.TASK_CARTESIAN, 6, lam=0.5, name="base")], [Task(abi.TASK_POSTURAL, n, lam=0.1, name="postural")]]
+    bounds = [Bound(abi.BOUND_JOINT_LIMITS, scaling=1.0, name="joint_limits"), Bound(abi.BOUND_VELOCITY_LIMITS, dT=0.05, name="velocity_limits")]
+    rowblocks = [Rows(abi.ROWS_GENERIC, 3, name="omni_wheels_4x")] if omni else []
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    qmin, qmax = np.full(n, -10.0), np.full(n, 10.0)
+    ident = np.tile(np.concatenate([np.eye(3).reshape(9), np.zeros(3)]), (B, 1))
+    leaf = {"B": B, "A": [z(B, 4 * legs, n), z(B, 6, n), None],
+            "task": [[(z(B, 4), None, None) for _ in range(legs)], [(ident.copy(), ident.copy(), None)], [(q0.copy(), q_ref, None)]],
+            "bound": [(q0.copy(), np.tile(qmin, (B, 1)), np.tile(qmax, (B, 1))), (np.full((B, n), 2.0), None, None)],
+            "rows": [(z(B, 3, n), z(B, 3), z(B, 3))] if omni else [], "C": [None] if omni else [],
+            "state": {"q0": q0, "q_ref": q_ref, "base_step": base_step}}
+    return plan, leaf, model
+
+
+def wheeled_outputs(model, omni):
+    """where the producer writes for make_wheeled_stack: (frame_pose, frame_J, rowset_A) as {index: ("A", level, first row) /
+    ("task", level, task) / ("C", block, first row)}"""
+    legs = len(model.wheel_joints)
+    rs = {i: ("A", 0, 4 * i) for i in range(legs)}
+    if omni:
+        rs[legs] = ("C", 0, 0)
+    return {0: ("task", 1, 0)}, {0: ("A", 1, 0)}, rs
+
+
+def bind_wheeled(stack, kin, leaf):
+    """wire make_wheeled_stack to the device: one q tensor is the producer's input, the Postural task's and the joint limits' q; the
+    producer writes the PureRolling rows into stack.A[0], the base's Jacobian into stack.A[1], its pose into the Cartesian task's leaf
+    and, for the omni variant, the OmniWheels4X rows into the row block's p0.  The base's reference is the first posture's pose moved
+    by leaf["state"]["base_step"].  -> (dev_leaf, kin_batch, q)"""
+    import torch
+    B = leaf["B"]
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q = torch.as_tensor(leaf["state"]["q0"], **f64).contiguous()
+    pose = torch.zeros((B, 12), **f64)
+    legs = len(kin.model.wheel_joints)
+    rs = {i: (stack.A[0], 4 * i) for i in range(legs)}
+    omni = len(kin.model.rowsets) > legs
+    if omni:
+        Crows = dev["rows"][0][0]
+        rs[legs] = (Crows, 0)
+    kw = dict(frame_pose={0: pose}, frame_J={0: (stack.A[1], 0)}, rowset_A=rs)
+    kin.forward(q, **kw)
+    ref = pose.clone()
+    ref[:, 9:] += torch.as_tensor(leaf["state"]["base_step"], **f64)
+    dev["task"][1][0] = (pose, ref, None)
+    dev["task"][2][0] = (q, dev["task"][2][0][1], None)
+    dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
+    return dev, kin.batch_args(q, **kw), q
+
+
+def _frame_lin_jacobian(model, q, f):
+    """numpy: world position p and linear Jacobian [3][n] of frame f's origin at q[n] (the recurrence of KinModel.points_world)"""
+    n = model.n
+    Rw, pw = np.zeros((n, 3, 3)), np.zeros((n, 3))
+    for j in range(n):
+        if model.jtype[j] == abi.JOINT_REVOLUTE:
+            x, y, z = model.axis[j]
+            c, s = np.cos(q[j]), np.sin(q[j])
+            K = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+            Rl, pl = model.R0[j] @ (np.eye(3) + s * K + (1.0 - c) * (K @ K)), model.p0[j]
+        else:
+            Rl, pl = model.R0[j], model.p0[j] + model.R0[j] @ model.axis[j] * q[j]
+        a = model.parent[j]
+        Rw[j], pw[j] = (Rl, pl) if a < 0 else (Rw[a] @ Rl, Rw[a] @ pl + pw[a])
+    _, jf, _, pf = model.frames[f]
+    p = pw[jf] + Rw[jf] @ np.asarray(pf, dtype=float)
+    J = np.zeros((3, n))
+    j = jf
+    while j >= 0:
+        zj = Rw[j] @ model.axis[j]
+        J[:, j] = np.cross(zj, p - pw[j]) if model.jtype[j] == abi.JOINT_REVOLUTE else zj
+        j = model.parent[j]
+    return p, J
+
+
+def make_base_estimation_stack(B, seed=None, legs=4, leg_joints=2, eps_factor=2e2):
+    """Floating-base estimation after examples/cpp/qp_estimation.cpp: a 6-variable plan whose one level holds a
+    tasks::floating_base::Contact per wheel, here a point contact (K = [I 0]: the 3 linear rows) on a frame "contact_<i>" fixed on
+    the rim of wheel i; A = (K Ad(R_f') J_f)[:, 0:6] and b = -(K Ad(R_f') J_f)[:, 6:] qdot[6:] are both written by the producer
+    (split contact row sets: A into A_0, b into the OSOT_TASK_GENERIC leaves).  The joint velocities qdot[6:] are made consistent with
+    a base twist planted in qdot[0:6] -- each leg's three joints carry its contact frame's velocity to zero -- so the least-squares
+    residual is zero and the solution is the planted twist.  eps_factor: iHQP's default regularisation (the answer is asked to 1e-9).
+    Returns (plan, leaf, model); leaf["state"] = q0, qdot."""
+    rng = np.random.default_rng(33000 if seed is None else seed)
+    model = make_wheeled_tree(legs, leg_joints)
+    n = model.n
+    K = np.eye(6)[:3]
+    model.frames = model.frames[:1]                       # the base; the wheel centres make room for the contact frames
+    for i, w in enumerate(model.wheel_joints):
+        model.frames.append((f"contact_{i}", w, np.eye(3), (WHEEL_RADIUS, 0.0, 0.0)))
+        model.add_contact_rows(f"contact_{i}", K, split=True)
+    q0 = wheeled_posture(model, B, seed=0 if seed is None else seed)
+    qdot = np.zeros((B, n))
+    qdot[:, :6] = rng.uniform(-0.5, 0.5, (B, 6))
+    per = leg_joints + 1
+    for i in range(B):
+        for k in range(legs):
+            _, J = _frame_lin_jacobian(model, q0[i], model.frame_index(f"contact_{k}"))
+            cols = list(range(6 + k * per, 6 + (k + 1) * per))
+            sol, *_ = np.linalg.lstsq(J[:, cols], -J[:, :6] @ qdot[i, :6], rcond=None)
+            qdot[i, cols] = sol
+            assert np.abs(J @ qdot[i]).max() < 1e-12, "a leg cannot hold its contact still: pick another posture"
+    z = lambda *sh: np.zeros(sh)
+    plan = StackPlan(n=6, levels=[[Task(abi.TASK_GENERIC, 3, name=f"contact_{i}") for i in range(legs)]],
+                     eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, 3 * legs, 6)], "task": [[(z(B, 3), None, None) for _ in range(legs)]], "bound": [], "rows": [], "C": [],
+            "state": {"q0": q0, "qdot": qdot}}
+    return plan, leaf, model
