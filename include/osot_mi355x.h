@@ -1019,6 +1019,89 @@ int osot_grad_destroy(osot_grad* g);
  * bound to a term beyond n_terms.  B == 0 is a no-op. */
 int osot_posture_gradient(osot_grad* g, const osot_grad_batch* batch, void* hip_stream);
 
+/* ---- force-space tasks: contact-wrench stacks ----------------------------------------------------------------------
+ * x = [w_0 .. w_{C-1} (6 each: force, torque) | optionally tau (nv - 6)]; wrench c starts at wrench_col[c], the torques at
+ * torque_col.  osot_force_rows turns the model quantities osot_kinematics / osot_dynamics leave on the device into the matrices
+ * and vectors of the reference's force tasks, written into OSOT_TASK_GENERIC / OSOT_ROWS_GENERIC blocks (no plan kind is added):
+ *   force::CoM (src/tasks/force/CoM.cpp:106-134, 176-207, 266-279), 6 rows:
+ *       block c of A = [I 0; P_c I], P_c = skew(p_c - com), p_c = the origin of contact c's frame;
+ *       b = [m (a_d + lambda2 (v_d - v) + lambda (p_d - com) - g); Ldot_d + lambda_ang (L_d - L)],
+ *       v = momentum[0:3] / m, L = momentum[3:6], m = mass
+ *   force::FloatingBase (FloatingBase.cpp:58-76), 6 rows: block c of A = (Jc_c[:, 0:6])'.  b is the caller's floating_base_torque,
+ *       a plain leaf: nothing is computed for it
+ *   constraints::force::StaticConstraint (StaticConstraint.cpp:17-34), nv - 6 equality rows: block c = (Jc_c[:, 6:nv])', the
+ *       identity on the torque columns (torque_col >= 0), beq = h_gravity[6:nv] - q_tau written to BOTH static_lo and static_up
+ *   force::Cartesian (Cartesian.cpp:34-65), b only: b = Kp e + Kd (v_ref - J_f qdot) + f_des on contact cart_contact (its frame,
+ *       its Jacobian, its wrench); A is the constant selection of the wrench's six columns (the caller's, written once).
+ *       e = [p_ref - p; e_o], e_o = -2 x the quaternion error of include/OpenSoT/utils/cartesian_utils.h:144-164 (the one
+ *       velocity::Cartesian uses, short path): it points from the actual to the reference orientation and is, to first order, the
+ *       rotation vector of R_ref R' (exactly 2 sin(theta / 2) x the axis).  XBot::Utils::computeOrientationError is not vendored:
+ *       parity with it is unpinned, as for every model quantity here.  cart_pose_error [B][6] replaces e for callers who bring
+ *       their own error.
+ *   force::Wrench / Wrenches (Force.cpp:5-26, 51-87) need no producer: A is the constant selection, b the reference.
+ * Each destination row receives exactly the columns of the C wrench blocks (for the static rows also the nv - 6 torque columns);
+ * every other column of the row, and the gaps between rows and instances, are left untouched (the cmm_ang convention of
+ * osot_dynamics), so the rows land in a zero-initialised A_k or C next to other blocks.
+ * enabled [B][C] (may be NULL = all): contact c of an instance with enabled == 0 gets an all-zero block in the CoM, FloatingBase
+ * and static rows (written as zeros, so a contact may be released and taken up again from cycle to cycle).  For FloatingBase this
+ * is setEnabledContacts.  For CoM it stands in for setLinksInContact: with lo = up = 0 wrench limits on the released contact the
+ * QP is the same problem as the one over the shorter contact list. */
+#define OSOT_FORCE_MAX_CONTACTS 8
+typedef struct {
+    int n_contacts;                          /* C, 1 .. OSOT_FORCE_MAX_CONTACTS                                              */
+    int nv;                                  /* coordinates of the tree, 6 .. OSOT_KIN_MAX_JOINTS (the first six: floating base) */
+    int n;                                   /* the plan's variable count, 1 .. OSOT_MAX_QP_VARS                             */
+    int wrench_col[OSOT_FORCE_MAX_CONTACTS]; /* first of the six columns of wrench c                                         */
+    int torque_col;                          /* first of the nv - 6 torque columns, -1 = x holds no torques                  */
+    int cart_contact;                        /* the contact force::Cartesian is on                                           */
+    double mass;                             /* total mass of the tree                                                       */
+    double gravity[3];                       /* world frame, e.g. (0, 0, -9.81)                                              */
+    double com_lambda, com_lambda2, com_lambda_ang;
+    double cart_Kp[36], cart_Kd[36];         /* row-major 6 x 6                                                              */
+} osot_force_model;
+typedef struct {
+    int B;
+    const double* pose[OSOT_FORCE_MAX_CONTACTS]; /* [B][12] pose of contact c's frame as osot_kinematics writes it (R row-major; p) */
+    const double* Jc;                        /* [B][C][6][nv] world Jacobians of the contact frames                          */
+    const double* com;                       /* [B][3]                                                                       */
+    const double* momentum;                  /* [B][6] centroidal momentum [linear; angular]                                 */
+    const double* h_gravity;                 /* [B][nv] h of osot_dynamics with qdot = NULL                                  */
+    const double* qdot;                      /* [B][nv], NULL = zero                                                         */
+    const int* enabled;                      /* [B][C], NULL = every contact enabled                                         */
+    double* com_A;                           /* first of the 6 rows of force::CoM in instance 0, or NULL                     */
+    long long com_A_stride;                  /* doubles from one instance to the next (>= 6 * ld)                            */
+    int com_A_ld;                            /* row length in doubles (>= n), 0 = n                                          */
+    double* com_b;                           /* 6 doubles per instance, or NULL                                              */
+    long long com_b_stride;                  /* (6 when dense)                                                               */
+    const double* com_pos_ref;               /* p_d [B][3]; NULL = the actual CoM                                            */
+    const double* com_vel_ref;               /* v_d [B][3]; NULL = zero                                                      */
+    const double* com_acc_ref;               /* a_d [B][3]; NULL = zero                                                      */
+    const double* ang_mom_ref;               /* L_d [B][3]; NULL = the actual momentum                                       */
+    const double* ang_mom_rate_ref;          /* Ldot_d [B][3]; NULL = zero                                                   */
+    double* fb_A;                            /* the 6 rows of force::FloatingBase, likewise                                  */
+    long long fb_A_stride;
+    int fb_A_ld;
+    double* static_A;                        /* the nv - 6 rows of StaticConstraint, likewise (stride >= (nv - 6) * ld)      */
+    long long static_A_stride;
+    int static_A_ld;
+    double* static_lo;                       /* nv - 6 doubles per instance each, both or neither                            */
+    double* static_up;
+    long long static_b_stride;               /* (nv - 6 when dense)                                                          */
+    const double* static_q_tau;              /* [B][nv - 6] constant of the torque variable; NULL = zero                     */
+    double* cart_b;                          /* 6 doubles per instance, or NULL                                              */
+    long long cart_b_stride;
+    const double* cart_pose_ref;             /* [B][12]                                                                      */
+    const double* cart_vel_ref;              /* [B][6]; NULL = zero                                                          */
+    const double* cart_f_des;                /* [B][6]; NULL = zero                                                          */
+    const double* cart_pose_error;           /* [B][6]: replaces e (cart_pose_ref is then not read)                          */
+} osot_force_batch;
+/* Stream-ordered, no allocation, capturable; B == 0 is a no-op.  Refused with OSOT_ERR_INVALID before any device is touched
+ * (osot_last_error() names the field): n_contacts outside 1 .. 8, nv below 6 or above 64, n out of range, static rows with
+ * nv == 6, a wrench_col / torque_col range that leaves 0 .. n-1, overlapping column ranges, a row length below n, a stride below
+ * rows * ld (below the vector's length for a b), references without the output they belong to, a non-finite gain, gravity or
+ * mass, an output without the inputs it is computed from. */
+int osot_force_rows(const osot_force_model* model, const osot_force_batch* batch, void* hip_stream);
+
 /* ---- layout of the structs above as THIS library was compiled (for bindings that mirror them by hand: ctypes, cgo, JNI ...).
  * name = the typedef's name ("osot_plan_desc", "osot_qp_batch", ...).  *size = sizeof; the byte offset of every member, in
  * declaration order, goes to offsets[0 .. *n_fields) (at most max_fields are written; offsets may be NULL).  Unknown name:

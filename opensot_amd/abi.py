@@ -207,13 +207,39 @@ class GradBatch(C.Structure):
                 ("value", C.c_void_p * GRAD_MAX_TERMS)]
 
 
+FORCE_MAX_CONTACTS = 8
+
+
+class ForceModel(C.Structure):
+    _fields_ = [("n_contacts", C.c_int), ("nv", C.c_int), ("n", C.c_int), ("wrench_col", C.c_int * FORCE_MAX_CONTACTS),
+                ("torque_col", C.c_int), ("cart_contact", C.c_int), ("mass", C.c_double), ("gravity", C.c_double * 3),
+                ("com_lambda", C.c_double), ("com_lambda2", C.c_double), ("com_lambda_ang", C.c_double),
+                ("cart_Kp", C.c_double * 36), ("cart_Kd", C.c_double * 36)]
+
+
+class ForceBatch(C.Structure):
+    _fields_ = [("B", C.c_int), ("pose", C.c_void_p * FORCE_MAX_CONTACTS), ("Jc", C.c_void_p), ("com", C.c_void_p),
+                ("momentum", C.c_void_p), ("h_gravity", C.c_void_p), ("qdot", C.c_void_p), ("enabled", C.c_void_p),
+                ("com_A", C.c_void_p), ("com_A_stride", C.c_longlong), ("com_A_ld", C.c_int),
+                ("com_b", C.c_void_p), ("com_b_stride", C.c_longlong),
+                ("com_pos_ref", C.c_void_p), ("com_vel_ref", C.c_void_p), ("com_acc_ref", C.c_void_p),
+                ("ang_mom_ref", C.c_void_p), ("ang_mom_rate_ref", C.c_void_p),
+                ("fb_A", C.c_void_p), ("fb_A_stride", C.c_longlong), ("fb_A_ld", C.c_int),
+                ("static_A", C.c_void_p), ("static_A_stride", C.c_longlong), ("static_A_ld", C.c_int),
+                ("static_lo", C.c_void_p), ("static_up", C.c_void_p), ("static_b_stride", C.c_longlong),
+                ("static_q_tau", C.c_void_p),
+                ("cart_b", C.c_void_p), ("cart_b_stride", C.c_longlong),
+                ("cart_pose_ref", C.c_void_p), ("cart_vel_ref", C.c_void_p), ("cart_f_des", C.c_void_p),
+                ("cart_pose_error", C.c_void_p)]
+
+
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
     "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
-    "osot_id_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_pure_rolling_s33", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
+    "osot_id_rows", "osot_force_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_pure_rolling_s33", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
     "osot_grad_create", "osot_grad_destroy", "osot_posture_gradient", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
     "osot_backend_create", "osot_backend_destroy", "osot_backend_init_problem",
     "osot_backend_update_task", "osot_backend_update_constraints", "osot_backend_update_bounds",
@@ -232,7 +258,8 @@ STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound
            "osot_plan_desc": PlanDesc, "osot_qp_batch": QpBatch, "osot_leaf_ptrs": LeafPtrs, "osot_leaf_batch": LeafBatch,
            "osot_assembled_out": AssembledOut, "osot_backend_options": BackendOptions, "osot_nhqp_options": NhqpOptions,
            "osot_admm_options": AdmmOptions, "osot_id_model": IdModel, "osot_kin_desc": KinDesc, "osot_kin_batch": KinBatch,
-           "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch, "osot_shape": Shape}
+           "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch, "osot_shape": Shape,
+           "osot_force_model": ForceModel, "osot_force_batch": ForceBatch}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -287,6 +314,7 @@ def lib():
     L.osot_solver_resident_waves_nhqp.argtypes = [vp, vp, ip]
     L.osot_id_force_gains.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, dp, dp, vp, vp, C.c_longlong, vp, vp]
     L.osot_id_rows.argtypes = [C.POINTER(IdModel), vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, vp, vp, vp, vp]
+    L.osot_force_rows.argtypes = [C.POINTER(ForceModel), C.POINTER(ForceBatch), vp]
     L.osot_computed_torque.argtypes = [C.POINTER(IdModel), vp, vp, vp, C.c_double, vp]
     L.osot_kin_create.argtypes = [C.POINTER(KinDesc), C.c_int, C.POINTER(vp)]
     L.osot_kin_destroy.argtypes = [vp]

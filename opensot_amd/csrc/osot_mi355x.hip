@@ -22,6 +22,7 @@
 #include "osot_control.h"
 #include "osot_ehqp.h"
 #include "osot_id.h"
+#include "osot_force.h"
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
 #include "osot_qp_big.h"
@@ -217,6 +218,14 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
     OSOT_LAYOUT_BEGIN(osot_grad_desc) OSOT_F(n_terms) OSOT_F(kind) OSOT_F(frame) OSOT_F(step) OSOT_F(lambda) OSOT_F(joint_mask)
         OSOT_F(W_diag) OSOT_F(gravity) OSOT_LAYOUT_END()
     OSOT_LAYOUT_BEGIN(osot_grad_batch) OSOT_F(B) OSOT_F(q) OSOT_F(b) OSOT_F(b_stride) OSOT_F(value) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_force_model) OSOT_F(n_contacts) OSOT_F(nv) OSOT_F(n) OSOT_F(wrench_col) OSOT_F(torque_col) OSOT_F(cart_contact)
+        OSOT_F(mass) OSOT_F(gravity) OSOT_F(com_lambda) OSOT_F(com_lambda2) OSOT_F(com_lambda_ang) OSOT_F(cart_Kp) OSOT_F(cart_Kd) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_force_batch) OSOT_F(B) OSOT_F(pose) OSOT_F(Jc) OSOT_F(com) OSOT_F(momentum) OSOT_F(h_gravity) OSOT_F(qdot)
+        OSOT_F(enabled) OSOT_F(com_A) OSOT_F(com_A_stride) OSOT_F(com_A_ld) OSOT_F(com_b) OSOT_F(com_b_stride) OSOT_F(com_pos_ref)
+        OSOT_F(com_vel_ref) OSOT_F(com_acc_ref) OSOT_F(ang_mom_ref) OSOT_F(ang_mom_rate_ref) OSOT_F(fb_A) OSOT_F(fb_A_stride) OSOT_F(fb_A_ld)
+        OSOT_F(static_A) OSOT_F(static_A_stride) OSOT_F(static_A_ld) OSOT_F(static_lo) OSOT_F(static_up) OSOT_F(static_b_stride)
+        OSOT_F(static_q_tau) OSOT_F(cart_b) OSOT_F(cart_b_stride) OSOT_F(cart_pose_ref) OSOT_F(cart_vel_ref) OSOT_F(cart_f_des)
+        OSOT_F(cart_pose_error) OSOT_LAYOUT_END()
 #undef OSOT_LAYOUT_BEGIN
 #undef OSOT_F
 #undef OSOT_LAYOUT_END
@@ -1527,6 +1536,17 @@ int osot_id_rows(const osot_id_model* m, double* C_dyn, long long dyn_stride, do
         R.J[i] = J[i]; R.J_rows[i] = J_rows[i]; R.A_dst[i] = A_dst[i]; R.A_stride[i] = A_stride[i];
     }
     hipLaunchKernelGGL(osot_id_rows_kernel, dim3((unsigned)m->B), dim3(64), 0, (hipStream_t)hip_stream, R);
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// force-space task rows (osot_force.h): force::CoM, force::FloatingBase, StaticConstraint, force::Cartesian
+int osot_force_rows(const osot_force_model* m, const osot_force_batch* b, void* hip_stream) {
+    const char* why = "";
+    const int rc = force_check(m, b, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_force_rows: ") + why);
+    if (b->B == 0) return OSOT_OK;
+    hipLaunchKernelGGL(osot_force_rows_kernel, dim3((unsigned)b->B), dim3(64), force_lds_bytes(m->n_contacts), (hipStream_t)hip_stream, *m, *b);
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

@@ -286,3 +286,177 @@ def force_gains(J, Bi, Kp, Kd, p0, rows, f_virtual=None, a_ref=None):
                                             Kd.ctypes.data_as(abi.dp), vp(f_virtual.data_ptr()) if f_virtual is not None else None,
                                             vp(p0.data_ptr() + 8 * 2 * rows), 2 * rows + 2 * rows * rows,
                                             vp(a_ref.data_ptr()) if a_ref is not None else None, st), "osot_id_force_gains")
+
+
+class ForceModel:
+    """osot_force_model (include/osot_mi355x.h: osot_force_rows): the layout of x = [w_0 .. w_{C-1} (6 each) | optionally tau (nv - 6)]
+    and the settings of the force tasks.  wrench_col: first column of every wrench (default 0, 6, ...); torque_col: first of the
+    nv - 6 torque columns or -1; com_gains = (lambda, lambda2, lambda_ang) of force::CoM; cart_contact, Kp, Kd (6 x 6, host) of
+    force::Cartesian.  Plumbing only: the arithmetic is in csrc/osot_force.h."""
+
+    def __init__(self, n_contacts, nv, n, wrench_col=None, torque_col=-1, mass=1.0, gravity=(0.0, 0.0, -9.81), com_gains=(1.0, 1.0, 1.0),
+                 cart_contact=0, Kp=None, Kd=None):
+        self.n_contacts, self.nv, self.n, self.torque_col = int(n_contacts), int(nv), int(n), int(torque_col)
+        self.wrench_col = [6 * c for c in range(self.n_contacts)] if wrench_col is None else [int(w) for w in wrench_col]
+        assert len(self.wrench_col) == self.n_contacts <= abi.FORCE_MAX_CONTACTS
+        m = abi.ForceModel()
+        m.n_contacts, m.nv, m.n, m.torque_col, m.cart_contact, m.mass = self.n_contacts, self.nv, self.n, self.torque_col, int(cart_contact), float(mass)
+        for c, w in enumerate(self.wrench_col):
+            m.wrench_col[c] = w
+        for i in range(3):
+            m.gravity[i] = float(gravity[i])
+        m.com_lambda, m.com_lambda2, m.com_lambda_ang = (float(g) for g in com_gains)
+        Kp = np.eye(6) if Kp is None else np.asarray(Kp, dtype=float).reshape(6, 6)
+        Kd = np.eye(6) if Kd is None else np.asarray(Kd, dtype=float).reshape(6, 6)
+        for i in range(36):
+            m.cart_Kp[i], m.cart_Kd[i] = float(Kp.reshape(36)[i]), float(Kd.reshape(36)[i])
+        self._m = m
+        self._lib = abi.lib()
+
+    def batch_args(self, B, Jc=None, pose=None, com=None, momentum=None, h_gravity=None, qdot=None, enabled=None,
+                   com_A=None, com_b=None, com_refs=None, fb_A=None, static_A=None, static_lo=None, static_up=None, static_q_tau=None,
+                   cart_b=None, cart_refs=None):
+        """the osot_force_batch of a call (pointers and strides; the tensors must outlive its use).  Inputs: Jc [B][C][6][nv], pose: a
+        list of C tensors [B][12], com [B][3], momentum [B][6], h_gravity [B][nv], qdot [B][nv], enabled int32 [B][C].
+        com_A / fb_A / static_A: (tensor [B][rows][ld], first row) like cmm_ang of Dynamics.batch_args (a bare tensor: row 0) -- a Generic
+        block's rows of stack.A[k], or the leaf p0 of an OSOT_ROWS_GENERIC block.  com_b / cart_b / static_lo / static_up: tensor
+        [B][>= width] or (tensor, first column), e.g. the leaf p0 of an OSOT_TASK_GENERIC block, p1 / p2 of an OSOT_ROWS_GENERIC block.
+        com_refs: dict(pos=, vel=, acc=, ang_mom=, ang_mom_rate=) of [B][3] tensors; cart_refs: dict(pose= [B][12], vel= [B][6],
+        f_des= [B][6], pose_error= [B][6])."""
+        C_, nv, n, na = self.n_contacts, self.nv, self.n, self.nv - 6
+        b = abi.ForceBatch()
+        b.B = B
+
+        def inp(t, shape, dtype=torch.float64):
+            assert t.is_contiguous() and t.dtype == dtype and t.shape[0] >= B and tuple(t.shape[1:]) == shape, (tuple(t.shape), shape)
+            return t.data_ptr()
+
+        def rows(t, nrows):
+            t, row = t if isinstance(t, tuple) else (t, 0)
+            assert t.is_contiguous() and t.dim() == 3 and t.dtype == torch.float64 and t.shape[0] >= B
+            assert row >= 0 and row + nrows <= t.shape[1] and t.shape[2] >= n
+            return t.data_ptr() + 8 * row * t.shape[2], t.shape[1] * t.shape[2], t.shape[2]
+
+        def place(t, width):
+            t, col = t if isinstance(t, tuple) else (t, 0)
+            assert t.is_contiguous() and t.dim() == 2 and t.dtype == torch.float64 and t.shape[0] >= B and col + width <= t.shape[1]
+            return t.data_ptr() + 8 * col, t.shape[1]
+        for c, p in enumerate(pose or ()):
+            b.pose[c] = inp(p, (12,))
+        for name, t, shape in (("Jc", Jc, (C_, 6, nv)), ("com", com, (3,)), ("momentum", momentum, (6,)), ("h_gravity", h_gravity, (nv,)),
+                               ("qdot", qdot, (nv,)), ("static_q_tau", static_q_tau, (na,))):
+            if t is not None:
+                setattr(b, name, inp(t, shape))
+        if enabled is not None:
+            b.enabled = inp(enabled, (C_,), torch.int32)
+        if com_A is not None:
+            b.com_A, b.com_A_stride, b.com_A_ld = rows(com_A, 6)
+        if fb_A is not None:
+            b.fb_A, b.fb_A_stride, b.fb_A_ld = rows(fb_A, 6)
+        if static_A is not None:
+            b.static_A, b.static_A_stride, b.static_A_ld = rows(static_A, na)
+        if static_lo is not None:
+            (b.static_lo, b.static_b_stride), (b.static_up, s2) = place(static_lo, na), place(static_up, na)
+            assert s2 == b.static_b_stride
+        if com_b is not None:
+            b.com_b, b.com_b_stride = place(com_b, 6)
+        for key, field in (("pos", "com_pos_ref"), ("vel", "com_vel_ref"), ("acc", "com_acc_ref"), ("ang_mom", "ang_mom_ref"),
+                           ("ang_mom_rate", "ang_mom_rate_ref")):
+            if (com_refs or {}).get(key) is not None:
+                setattr(b, field, inp(com_refs[key], (3,)))
+        if cart_b is not None:
+            b.cart_b, b.cart_b_stride = place(cart_b, 6)
+        for key, field, w in (("pose", "cart_pose_ref", 12), ("vel", "cart_vel_ref", 6), ("f_des", "cart_f_des", 6), ("pose_error", "cart_pose_error", 6)):
+            if (cart_refs or {}).get(key) is not None:
+                setattr(b, field, inp(cart_refs[key], (w,)))
+        return b
+
+    def write_rows(self, batch, device=None):
+        """osot_force_rows, stream-ordered on torch's current stream"""
+        st = C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+        abi.check(self._lib.osot_force_rows(C.byref(self._m), C.byref(batch), st), "osot_force_rows")
+
+
+def wrench_selection(n, wrench_cols):
+    """the constant A of force::Wrench / Wrenches and of force::Cartesian (Force.cpp:5-26, 51-87): the selection of the listed
+    wrenches' six columns, [6 len(wrench_cols)][n] -- written once into an OSOT_TASK_GENERIC block, its b is the reference"""
+    A = np.zeros((6 * len(wrench_cols), n))
+    for i, w in enumerate(wrench_cols):
+        A[6 * i:6 * i + 6, w:w + 6] = np.eye(6)
+    return A
+
+
+class ForceStep:
+    """One device-resident wrench-distribution cycle of a stack made by synth.make_coman_force_stack / make_wide_force_stack:
+        q, qdot -> osot_kinematics + osot_dynamics (momentum) + osot_dynamics (qdot = NULL: the gravity term) -> osot_force_rows -> osot_cycle
+    produce() runs the three producer launches; consume() everything behind them, reading ONLY the tensors the producers fill
+    (pose, Jc, com, momentum, h_gravity) -- so a caller may fill those from another source instead (kin_model=None: the stack
+    carries no tree; leaf["force"]["quantities"] is uploaded once).  The rows land in the OSOT_TASK_GENERIC / OSOT_ROWS_GENERIC blocks
+    leaf["force"] names: force::CoM or force::FloatingBase at level 0 of stack.A, the StaticConstraint rows in its block's leaf
+    (C, lo, up).  force::FloatingBase's b, the caller's floating_base_torque, is the floating-base part of the gravity term.
+    enabled [B][C] int32 and com_refs (zero tensors: p_d = the first CoM after the first produce()) are the caller's to rewrite.
+    Every launch goes to torch's current stream; nothing allocates after the constructor, so step() can be captured into a graph."""
+
+    def __init__(self, plan, leaf, kin_model=None, device=0, gravity=(0.0, 0.0, -9.81)):
+        from .solver import BatchedStack
+        f = leaf["force"]
+        B, nv, C_ = leaf["B"], f["nv"], len(f["wrench_col"])
+        self.B, self.nv, self.plan, self.form = B, nv, plan, f["form"]
+        self.st = BatchedStack(plan, B, device=device)
+        self.dev = self.st.load_leaf(leaf)
+        d = self.st.device
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(d)
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=d)
+        self.pose = [z(B, 12) for _ in range(C_)]
+        self.Jc, self.com, self.momentum, self.h_gravity = z(B, C_, 6, nv), z(B, 3), z(B, 6), z(B, nv)
+        self.enabled = torch.ones((B, C_), dtype=torch.int32, device=d)
+        self.kin = self.dyn = None
+        if kin_model is not None:
+            from .kinematics import Kinematics
+            self.q, self.qdot = t(leaf["state"]["q0"]), t(leaf["state"]["qdot0"])
+            self.kin, self.dyn = Kinematics(kin_model, device), Dynamics(kin_model, device, gravity)
+            frames = [kin_model.frame_index(c) for c in f["contacts"]]
+            J = self.Jc.view(B, 6 * C_, nv)
+            self._kb = self.kin.batch_args(self.q, frame_pose={fr: self.pose[c] for c, fr in enumerate(frames)},
+                                           frame_J={fr: (J, 6 * c) for c, fr in enumerate(frames)}, com=self.com)
+            self._db_mom = self.dyn.batch_args(self.q, self.qdot, momentum=self.momentum)
+            self._db_grav = self.dyn.batch_args(self.q, None, h=self.h_gravity)
+        else:
+            Q = f["quantities"]
+            for c in range(C_):
+                self.pose[c].copy_(t(Q["pose"][c]))
+            self.Jc.copy_(t(Q["Jc"])); self.com.copy_(t(Q["com"])); self.momentum.copy_(t(Q["momentum"])); self.h_gravity.copy_(t(Q["h_gravity"]))
+        self.model = ForceModel(C_, nv, plan.n, f["wrench_col"], f["torque_col"], mass=f["mass"], gravity=gravity, com_gains=f["com_gains"])
+        self.com_refs = dict(pos=z(B, 3), vel=z(B, 3), acc=t(f["com_acc_ref"]) if f.get("com_acc_ref") is not None else z(B, 3),
+                             ang_mom=z(B, 3), ang_mom_rate=z(B, 3))
+        self._com_ref_set = False
+        kw = dict(Jc=self.Jc, pose=self.pose, com=self.com, momentum=self.momentum, h_gravity=self.h_gravity, enabled=self.enabled)
+        lvl, row = f["task"]
+        self.b0 = self.dev["task"][lvl][f["task_index"]][0]            # leaf p0 of the level's force block: its b
+        if self.form == "com":
+            kw.update(com_A=(self.st.A[lvl], row), com_b=self.b0, com_refs=self.com_refs)
+        else:
+            kw.update(fb_A=(self.st.A[lvl], row))
+        if f.get("static_block") is not None:
+            Cs, lo, up = self.dev["rows"][f["static_block"]]
+            kw.update(static_A=Cs, static_lo=lo, static_up=up)
+        self._fb = self.model.batch_args(B, **kw)
+
+    def produce(self):
+        self.kin.forward(self.q, batch=self._kb)
+        self.dyn.forward(self.q, batch=self._db_mom)
+        self.dyn.forward(self.q, batch=self._db_grav)
+
+    def consume(self):
+        if not self._com_ref_set:                       # p_d: the first CoM (host-side flag: set before a capture)
+            self.com_refs["pos"].copy_(self.com)
+            self._com_ref_set = True
+        if self.form != "com":
+            self.b0.copy_(self.h_gravity[:, :6])        # floating_base_torque: a plain leaf
+        self.model.write_rows(self._fb, self.st.device)
+        self.st.cycle(self.dev)
+
+    def step(self, producers=True):
+        if producers and self.kin is not None:
+            self.produce()
+        self.consume()

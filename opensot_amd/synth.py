@@ -1409,3 +1409,108 @@ def make_base_estimation_stack(B, seed=None, legs=4, leg_joints=2, eps_factor=2e
     leaf = {"B": B, "A": [z(B, 3 * legs, 6)], "task": [[(z(B, 3), None, None) for _ in range(legs)]], "bound": [], "rows": [], "C": [],
             "state": {"q0": q0, "qdot": qdot}}
     return plan, leaf, model
+
+
+# ---- the force-space tasks: wrench distribution over surface contacts (rows from osot_force_rows) --------------------------------------
+def _force_rowblocks(B, C_, mu, R9, lims, wrench_max=(1.0e3, 1.0e3, 1.0e3, 200.0, 200.0, 200.0)):
+    """force::FrictionCone, force::CoP on the C wrenches at columns 0 .. 6 C - 1 and force::WrenchLimits as unit rows"""
+    wl = np.tile(np.asarray(wrench_max, dtype=float), (B, C_))
+    blocks = [Rows(abi.ROWS_WRENCH_FRICTION_CONE, 5 * C_, first_col=0, mu=mu, name="friction_cones"),
+              Rows(abi.ROWS_COP, 4 * C_, first_col=0, name="cop"),
+              Rows(abi.ROWS_UNIT_GENERIC, 6 * C_, first_col=0, name="wrench_limits")]
+    return blocks, [(R9, None, None), (R9, lims, None), (-wl, wl, None)]
+
+
+def make_coman_force_stack(B, form="com", seed=None, tree=None, inertia=None, com_acc=0.2, eps_factor=1e6):
+    """The reference's wrench-distribution stack on its COMAN standing on both soles (surface contacts l_sole, r_sole; the posture of
+    make_coman_id_stack, at rest), x = [w_l_sole (6); w_r_sole (6) | tau (29)]:
+
+      form "com"    (n = 12): level 0 = force::CoM (6 rows [I 0; P_c I] per contact, b from the CoM references), level 1 = force::Wrenches
+                    (the selection I_12, b = the reference wrenches: half the weight on each sole); global rows: force::FrictionCone,
+                    force::CoP, force::WrenchLimits
+      form "static" (n = 41): the torques join x; level 0 = force::FloatingBase ((Jc_c[:, 0:6])' per contact, b = the floating-base
+                    part of the gravity term) in place of force::CoM, level 1 as above; the StaticConstraint's 29 equality rows
+                    [(Jc_c[:, 6:35])' I] x = g[6:35] come first among the global rows
+    Every force block is OSOT_TASK_GENERIC / OSOT_ROWS_GENERIC and arrives zeroed: opensot_amd.dynamics.ForceStep has osot_kinematics,
+    osot_dynamics and osot_force_rows write them every cycle.  The CoM reference asks for up to com_acc m/s^2 of acceleration from
+    the first CoM.  Returns (plan, leaf, model); leaf["force"] names the blocks for ForceStep, leaf["state"] = q0, qdot0."""
+    assert form in ("com", "static")
+    _, idleaf, model = make_coman_id_stack(B, seed=seed, tree=tree, inertia=inertia)
+    rng = np.random.default_rng(41000 if seed is None else seed)
+    nv, C_ = model.n, 2
+    na = nv - 6
+    n = 12 + (na if form == "static" else 0)
+    mass = float(np.sum(model.mass))
+    z = lambda *sh: np.zeros(sh)
+    w_ref = np.tile(np.array([0.0, 0.0, 0.5 * mass * 9.81, 0.0, 0.0, 0.0]), (B, C_))
+    levels = [[Task(abi.TASK_GENERIC, 6, name="force_com" if form == "com" else "floating_base")],
+              [Task(abi.TASK_GENERIC, 12, name="wrenches")]]
+    Asel = np.zeros((12, n)); Asel[:, :12] = np.eye(12)
+    R9 = np.tile(np.eye(3).reshape(9), (B, C_, 1))
+    lims = np.tile(np.array(SOLE_RECTANGLE), (B, C_, 1))
+    rowblocks, rleaf = _force_rowblocks(B, C_, 0.8, R9, lims)
+    Cl = [None] * 3
+    static_block = None
+    if form == "static":
+        rowblocks.insert(0, Rows(abi.ROWS_GENERIC, na, name="static_constraint"))
+        rleaf.insert(0, (z(B, na, n), z(B, na), z(B, na)))
+        Cl.insert(0, None)
+        static_block = 0
+    plan = StackPlan(n=n, levels=levels, bounds=[], rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, 6, n), np.tile(Asel, (B, 1, 1))], "task": [[(z(B, 6), None, None)], [(w_ref, None, None)]],
+            "bound": [], "rows": rleaf, "C": Cl,
+            "state": {"q0": idleaf["state"]["q0"], "qdot0": z(B, nv)},
+            "force": {"form": form, "nv": nv, "wrench_col": [0, 6], "torque_col": 12 if form == "static" else -1, "contacts": ("l_sole", "r_sole"),
+                      "mass": mass, "com_gains": (25.0, 10.0, 1.0), "task": (0, 0), "task_index": 0, "static_block": static_block,
+                      "com_acc_ref": rng.uniform(-com_acc, com_acc, (B, 3))}}
+    return plan, leaf, model
+
+
+def make_wide_force_stack(B, seed=None, nv=64, n_contacts=8, eps_factor=1e6):
+    """The "static" form of make_coman_force_stack at the producer's limits, on synthetic model quantities: nv = 64 coordinates, eight
+    surface contacts, x = [8 wrenches (48); tau (58)], n = 106 -- the wide route (osot_solver_create_wide).  No tree: leaf["force"]
+    ["quantities"] holds pose, Jc, com, momentum, h_gravity (what the producers would write), made so that a nominal wrench set W0
+    strictly inside every cone and CoP rectangle balances the gravity term (asserted): h_gravity = sum_c Jc_c' W0_c + [0; tau0].
+    level 0 = force::FloatingBase, level 1 = force::Wrenches with references near W0; rows: StaticConstraint (58 equalities),
+    force::FrictionCone, force::CoP, force::WrenchLimits.  Returns (plan, leaf, None) for dynamics.ForceStep(kin_model=None)."""
+    rng = np.random.default_rng(43000 if seed is None else seed)
+    C_, na = n_contacts, nv - 6
+    nf = 6 * C_
+    n = nf + na
+    assert n <= abi.MAX_QP_VARS and C_ <= abi.FORCE_MAX_CONTACTS
+    mu = 0.8
+    Jc = np.zeros((B, C_, 6, nv))
+    Jc[:, :, :, :6] = rng.normal(0.0, 0.5, size=(B, C_, 6, 6))
+    for ct in range(C_):
+        cols = 6 + (7 * ct + np.arange(7)) % na
+        Jc[:, ct][:, :, cols] = rng.normal(0.0, 0.3, size=(B, 6, 7))
+    wRl = _rot_exp(rng.normal(0.0, 0.15, size=(B, C_, 3)))
+    lims = np.stack([rng.uniform(-0.12, -0.08, size=(B, C_)), rng.uniform(0.10, 0.15, size=(B, C_)),
+                     rng.uniform(-0.07, -0.05, size=(B, C_)), rng.uniform(0.05, 0.07, size=(B, C_))], axis=2)
+    fz = rng.uniform(40.0, 80.0, size=(B, C_))
+    f_loc = np.stack([rng.uniform(-3, 3, size=(B, C_)), rng.uniform(-3, 3, size=(B, C_)), fz], axis=2)
+    cx = (lims[..., 0] + lims[..., 1]) / 2 + rng.uniform(-0.01, 0.01, size=(B, C_))
+    cy = (lims[..., 2] + lims[..., 3]) / 2 + rng.uniform(-0.01, 0.01, size=(B, C_))
+    t_loc = np.stack([cy * fz, -cx * fz, rng.uniform(-0.3, 0.3, size=(B, C_))], axis=2)
+    W0 = np.concatenate([np.einsum("bcij,bcj->bci", wRl, f_loc), np.einsum("bcij,bcj->bci", wRl, t_loc)], axis=2)
+    for kind in (abi.ROWS_WRENCH_FRICTION_CONE, abi.ROWS_COP):
+        for ct in range(C_):
+            v = np.einsum("brj,bj->br", wrench_rows(kind, wRl[:, ct], lims[:, ct], mu), W0[:, ct])
+            assert v.max() < -1e-3, (kind, ct, v.max())
+    h = np.einsum("bcij,bci->bj", Jc, W0) + np.concatenate([np.zeros((B, 6)), rng.normal(0.0, 5.0, size=(B, na))], axis=1)
+    pose = [np.concatenate([wRl[:, ct].reshape(B, 9), rng.uniform(-0.5, 0.5, (B, 3))], axis=1) for ct in range(C_)]
+    z = lambda *sh: np.zeros(sh)
+    levels = [[Task(abi.TASK_GENERIC, 6, name="floating_base")], [Task(abi.TASK_GENERIC, nf, name="wrenches")]]
+    Asel = np.zeros((nf, n)); Asel[:, :nf] = np.eye(nf)
+    w_ref = W0.reshape(B, nf) + rng.normal(0.0, 1.0, size=(B, nf))
+    rowblocks, rleaf = _force_rowblocks(B, C_, mu, np.ascontiguousarray(wRl.reshape(B, C_, 9)), np.ascontiguousarray(lims))
+    rowblocks.insert(0, Rows(abi.ROWS_GENERIC, na, name="static_constraint"))
+    rleaf.insert(0, (z(B, na, n), z(B, na), z(B, na)))
+    plan = StackPlan(n=n, levels=levels, bounds=[], rowblocks=rowblocks, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, 6, n), np.tile(Asel, (B, 1, 1))], "task": [[(z(B, 6), None, None)], [(w_ref, None, None)]],
+            "bound": [], "rows": rleaf, "C": [None] * 4,
+            "force": {"form": "static", "nv": nv, "wrench_col": [6 * c for c in range(C_)], "torque_col": nf, "contacts": None,
+                      "mass": 60.0, "com_gains": (25.0, 10.0, 1.0), "task": (0, 0), "task_index": 0, "static_block": 0,
+                      "quantities": {"pose": pose, "Jc": Jc, "com": rng.uniform(-0.2, 0.2, (B, 3)), "momentum": z(B, 6), "h_gravity": h},
+                      "nominal": W0.reshape(B, nf)}}
+    return plan, leaf, None
