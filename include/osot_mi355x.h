@@ -1102,6 +1102,111 @@ typedef struct {
  * mass, an output without the inputs it is computed from. */
 int osot_force_rows(const osot_force_model* model, const osot_force_batch* batch, void* hip_stream);
 
+/* ---- tasks driven by measurements: admittance, IMU, contact error, collision task ------------------------------------
+ * osot_feedback turns sensor readings and the model quantities osot_kinematics / osot_dynamics leave on the device into the
+ * references and rows of five reference classes, written into the leaves of existing kinds (no plan kind is added).  It is a
+ * launch of its own in front of osot_cycle.  Every group below is optional: a group whose output is NULL is skipped.
+ *   1. velocity::CartesianAdmittance (src/tasks/velocity/CartesianAdmittance.cpp:50-77), per term t < n_cart, R = cart_pose[t][0:9]:
+ *        e = [R f; R m] of cart_wrench[t] = [f; m] measured in the sensor frame.  XBot::Utils::adjointFromRotation is not vendored:
+ *        it is taken as blockdiag(R, R), parity with it is unpinned, as for every model quantity here.
+ *        dead zone per channel (apply_deadzone, :303-320): e > dz -> e - dz, e < -dz -> e + dz, otherwise 0
+ *        e -= cart_wrench_ref[t]
+ *        y = filter(e)   (below)
+ *        cart_twist_out[t] = cart_twist_in[t] + cart_C o y: the desired twist (p2) of the OSOT_TASK_CARTESIAN leaf
+ *   2. velocity::JointAdmittance (JointAdmittance.cpp:28-44): u = joint_h - joint_tau, y = filter(u) with one set of
+ *        coefficients, joint_qdot_out = C y, the desired velocity (p2) of the OSOT_TASK_POSTURAL leaf.  C = joint_C [nv][nv]
+ *        row-major, one matrix for the batch (row i: an fma chain over j = 0 .. nv-1 from 0), or joint_C_scalar * I where joint_C
+ *        is NULL (c * y_i).  With floating_base, entries 0 .. 5 are written as zeros.
+ *   3. floating_base::IMU (src/tasks/floating_base/IMU.cpp:33-42): rows 0 .. 2 of imu_A are zeros, rows 3 .. 5 are
+ *        imu_fb_J[3:6][0:6] (the floating-base link's frame_J); imu_b = [0; R_imu omega].  Columns 0 .. 5 only: any other column
+ *        of a longer row, and the gaps between rows and instances, are left untouched (the cmm_ang convention of osot_dynamics).
+ *   4. floating_base::Contact, the lambda * err term (src/tasks/floating_base/Contact.cpp:55-66):
+ *        contact_b_out = contact_b_in + contact_lambda * [p_d - p; -e_o], contact_b_in = what rowset_b of osot_kinematics received,
+ *        e_o = the quaternion error of include/OpenSoT/utils/cartesian_utils.h:144-164 on the short path, from contact_pose to
+ *        contact_pose_ref: the 6-vector velocity::Cartesian's b holds at lambda = 1, orientation gain 1.
+ *   5. tasks::velocity::CollisionAvoidance (src/tasks/velocity/CollisionAvoidance.cpp:17-47), per pair row i:
+ *        err = ca_dist[i] - ca_threshold; err > 0: row i of ca_A (n columns) and ca_b[i] are written as zeros; otherwise
+ *        ca_A[i] = -ca_J[i], ca_b[i] = err (err == 0 counts as violated).  ca_J / ca_dist are pair_J / pair_dist of osot_kinematics.
+ * THE FILTER (SecondOrderFilter, include/OpenSoT/tasks/velocity/CartesianAdmittance.h:27-137): per channel
+ *        a0 = 1 + 4 eps / (omega ts) + 4 / (omega ts)^2,  a1 = 2 - 8 / (omega ts)^2,  a2 = 1 + 4 / (omega ts)^2 - 4 eps / (omega ts)
+ *        (computed on the host inside the call, with the reference's expression);
+ *        shift ydd <- yd, yd <- y, udd <- ud, ud <- u, u <- input;  y = 1.0 / a0 * (u + 2 ud + 1 udd - a1 yd - a2 ydd), left to right.
+ * THE STATE: state [B][count], count = osot_feedback_state_doubles, caller-owned, read and rewritten by every call that has
+ * admittance terms.  Per instance: term t at 24 t as u[6], ud[6], y[6], yd[6]; the joint filter behind the last term as u[nv],
+ * ud[nv], y[nv], yd[nv] (udd and ydd are overwritten before they are read: not stored).  All zeros is a fresh filter (the
+ * reference's lazy reset(input * 0)); u = ud = y = yd = v is reset(v).  A term whose cart_twist_out is NULL keeps its state.
+ * The filter recurrence, the rotations and item 4 are compiled with floating-point contraction off: the same bits wherever the
+ * header is compiled. */
+#define OSOT_FEEDBACK_MAX_CART 8
+typedef struct {
+    int nv;                                  /* coordinates of the tree, 1 .. OSOT_KIN_MAX_JOINTS                            */
+    int floating_base;                       /* 0 / 1: the first six coordinates are the floating base                       */
+    int n_cart;                              /* Cartesian admittance terms, 0 .. OSOT_FEEDBACK_MAX_CART                      */
+    int joint;                               /* 0 / 1: the joint admittance filter exists                                    */
+    int imu;                                 /* 0 / 1                                                                        */
+    int n_pairs;                             /* collision pair rows, 0 .. OSOT_KIN_MAX_PAIRS                                 */
+    int n;                                   /* row length of ca_J and ca_A, 1 .. OSOT_MAX_QP_VARS (read with n_pairs > 0)   */
+    double cart_C[OSOT_FEEDBACK_MAX_CART * 6];        /* [t][6] compliance (diagonal)                                        */
+    double cart_deadzone[OSOT_FEEDBACK_MAX_CART * 6]; /* [t][6], >= 0                                                        */
+    double cart_omega[OSOT_FEEDBACK_MAX_CART * 6];    /* [t][6] natural frequency of each channel's filter, > 0              */
+    double cart_damping[OSOT_FEEDBACK_MAX_CART * 6];  /* [t][6] damping ratio eps, >= 0                                      */
+    double cart_ts[OSOT_FEEDBACK_MAX_CART];           /* [t] time step of the term's filters, > 0                            */
+    double joint_omega, joint_damping, joint_ts, joint_C_scalar;
+    double contact_lambda;
+    double ca_threshold;
+} osot_feedback_model;
+typedef struct {
+    int B;
+    double* state;                                        /* [B][count]; required where n_cart + joint > 0               */
+    const double* cart_pose[OSOT_FEEDBACK_MAX_CART];      /* [B][12] pose of the sensor frame as osot_kinematics writes it
+                                                             (relative to a base link: the producer's frame_base)        */
+    const double* cart_wrench[OSOT_FEEDBACK_MAX_CART];    /* [B][6] measured, in the sensor frame                         */
+    const double* cart_wrench_ref[OSOT_FEEDBACK_MAX_CART];/* [B][6]; NULL = zero                                          */
+    const double* cart_twist_in[OSOT_FEEDBACK_MAX_CART];  /* [B][6] the user's own desired twist; NULL = zero             */
+    double* cart_twist_out[OSOT_FEEDBACK_MAX_CART];       /* [B][6]; must not alias cart_twist_in                         */
+    const double* joint_tau;                              /* [B][nv] measured joint torques                               */
+    const double* joint_h;                                /* [B][nv] h of osot_dynamics                                   */
+    const double* joint_C;                                /* [nv][nv] row-major, one for the batch; NULL = joint_C_scalar I */
+    double* joint_qdot_out;                               /* [B][nv]                                                      */
+    const double* imu_fb_J;                               /* first of the 6 rows (length nv) of the floating-base link's
+                                                             Jacobian in instance 0                                       */
+    long long imu_fb_J_stride;                            /* doubles from one instance to the next (>= 6 nv)              */
+    const double* imu_pose;                               /* [B][12] pose of the IMU's link                               */
+    const double* imu_omega;                              /* [B][3] gyroscope reading, in the IMU's frame                 */
+    double* imu_A;                                        /* first of the 6 rows in instance 0                            */
+    long long imu_A_stride;                               /* (>= 6 ld)                                                    */
+    int imu_A_ld;                                         /* row length in doubles (>= 6), 0 = 6                          */
+    double* imu_b;                                        /* 6 doubles per instance                                       */
+    long long imu_b_stride;                               /* (>= 6)                                                       */
+    const double* contact_pose;                           /* [B][12]                                                      */
+    const double* contact_pose_ref;                       /* [B][12] the desired contact pose                             */
+    const double* contact_b_in;                           /* 6 doubles per instance                                       */
+    long long contact_b_in_stride;                        /* (>= 6)                                                       */
+    double* contact_b_out;                                /* 6 doubles per instance: the OSOT_TASK_GENERIC leaf; must not
+                                                             alias contact_b_in (a repeated call gives the same result)   */
+    long long contact_b_out_stride;                       /* (>= 6)                                                       */
+    const double* ca_J;                                   /* first of the n_pairs rows (length n) in instance 0           */
+    long long ca_J_stride;                                /* (>= n_pairs n)                                               */
+    const double* ca_dist;                                /* [B][n_pairs]                                                 */
+    double* ca_A;                                         /* first of the n_pairs rows in instance 0; must not be ca_J    */
+    long long ca_A_stride;                                /* (>= n_pairs ld)                                              */
+    int ca_A_ld;                                          /* row length in doubles (>= n), 0 = n                          */
+    double* ca_b;                                         /* n_pairs doubles per instance                                 */
+    long long ca_b_stride;                                /* (>= n_pairs)                                                 */
+} osot_feedback_batch;
+/* Stream-ordered, no allocation, capturable; B == 0 is a no-op.  Refused with OSOT_ERR_INVALID before any device is touched
+ * (osot_last_error() names the field): a size out of range, a flag that is not 0 / 1, a filter constant that is not positive
+ * and finite (damping and dead zone: negative), a non-finite gain, state NULL with n_cart + joint > 0, a pointer bound to a
+ * term beyond n_cart or to a group the model does not have, an output without its inputs, an input without its output, an
+ * output that aliases its input, a row length or a stride below what the rows need. */
+int osot_feedback(const osot_feedback_model* model, const osot_feedback_batch* batch, void* hip_stream);
+/* HOST only.  *count = doubles of filter state per instance: 4 (u, ud, y, yd) per channel, 6 n_cart channels, plus nv with joint. */
+int osot_feedback_state_doubles(const osot_feedback_model* model, int* count);
+/* HOST only.  CartesianAdmittance::computeParameters (CartesianAdmittance.cpp:171-199) as it is written: C = lambda K^-1,
+ * M = (dt / lambda) D - (dt dt / lambda) C^-1, w = dt (C M)^-1 (w: the omega of the term's filters).  OSOT_ERR_INVALID where
+ * D[i] <= K[i] dt / lambda for some i (nothing is written), or an argument is NULL. */
+int osot_admittance_params(const double K[6], const double D[6], double lambda, double dt, double C[6], double M[6], double w[6]);
+
 /* ---- layout of the structs above as THIS library was compiled (for bindings that mirror them by hand: ctypes, cgo, JNI ...).
  * name = the typedef's name ("osot_plan_desc", "osot_qp_batch", ...).  *size = sizeof; the byte offset of every member, in
  * declaration order, goes to offsets[0 .. *n_fields) (at most max_fields are written; offsets may be NULL).  Unknown name:

@@ -233,13 +233,42 @@ class ForceBatch(C.Structure):
                 ("cart_pose_error", C.c_void_p)]
 
 
+FEEDBACK_MAX_CART = 8
+
+
+class FeedbackModel(C.Structure):
+    _fields_ = [("nv", C.c_int), ("floating_base", C.c_int), ("n_cart", C.c_int), ("joint", C.c_int), ("imu", C.c_int),
+                ("n_pairs", C.c_int), ("n", C.c_int),
+                ("cart_C", C.c_double * (6 * FEEDBACK_MAX_CART)), ("cart_deadzone", C.c_double * (6 * FEEDBACK_MAX_CART)),
+                ("cart_omega", C.c_double * (6 * FEEDBACK_MAX_CART)), ("cart_damping", C.c_double * (6 * FEEDBACK_MAX_CART)),
+                ("cart_ts", C.c_double * FEEDBACK_MAX_CART),
+                ("joint_omega", C.c_double), ("joint_damping", C.c_double), ("joint_ts", C.c_double), ("joint_C_scalar", C.c_double),
+                ("contact_lambda", C.c_double), ("ca_threshold", C.c_double)]
+
+
+class FeedbackBatch(C.Structure):
+    _fields_ = [("B", C.c_int), ("state", C.c_void_p),
+                ("cart_pose", C.c_void_p * FEEDBACK_MAX_CART), ("cart_wrench", C.c_void_p * FEEDBACK_MAX_CART),
+                ("cart_wrench_ref", C.c_void_p * FEEDBACK_MAX_CART), ("cart_twist_in", C.c_void_p * FEEDBACK_MAX_CART),
+                ("cart_twist_out", C.c_void_p * FEEDBACK_MAX_CART),
+                ("joint_tau", C.c_void_p), ("joint_h", C.c_void_p), ("joint_C", C.c_void_p), ("joint_qdot_out", C.c_void_p),
+                ("imu_fb_J", C.c_void_p), ("imu_fb_J_stride", C.c_longlong), ("imu_pose", C.c_void_p), ("imu_omega", C.c_void_p),
+                ("imu_A", C.c_void_p), ("imu_A_stride", C.c_longlong), ("imu_A_ld", C.c_int),
+                ("imu_b", C.c_void_p), ("imu_b_stride", C.c_longlong),
+                ("contact_pose", C.c_void_p), ("contact_pose_ref", C.c_void_p), ("contact_b_in", C.c_void_p),
+                ("contact_b_in_stride", C.c_longlong), ("contact_b_out", C.c_void_p), ("contact_b_out_stride", C.c_longlong),
+                ("ca_J", C.c_void_p), ("ca_J_stride", C.c_longlong), ("ca_dist", C.c_void_p),
+                ("ca_A", C.c_void_p), ("ca_A_stride", C.c_longlong), ("ca_A_ld", C.c_int),
+                ("ca_b", C.c_void_p), ("ca_b_stride", C.c_longlong)]
+
+
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
     "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
-    "osot_id_rows", "osot_force_rows", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_pure_rolling_s33", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
+    "osot_id_rows", "osot_force_rows", "osot_feedback", "osot_feedback_state_doubles", "osot_admittance_params", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_pure_rolling_s33", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
     "osot_grad_create", "osot_grad_destroy", "osot_posture_gradient", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
     "osot_backend_create", "osot_backend_destroy", "osot_backend_init_problem",
     "osot_backend_update_task", "osot_backend_update_constraints", "osot_backend_update_bounds",
@@ -259,7 +288,8 @@ STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound
            "osot_assembled_out": AssembledOut, "osot_backend_options": BackendOptions, "osot_nhqp_options": NhqpOptions,
            "osot_admm_options": AdmmOptions, "osot_id_model": IdModel, "osot_kin_desc": KinDesc, "osot_kin_batch": KinBatch,
            "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch, "osot_shape": Shape,
-           "osot_force_model": ForceModel, "osot_force_batch": ForceBatch}
+           "osot_force_model": ForceModel, "osot_force_batch": ForceBatch,
+           "osot_feedback_model": FeedbackModel, "osot_feedback_batch": FeedbackBatch}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -315,6 +345,9 @@ def lib():
     L.osot_id_force_gains.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, dp, dp, vp, vp, C.c_longlong, vp, vp]
     L.osot_id_rows.argtypes = [C.POINTER(IdModel), vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, vp, vp, vp, vp]
     L.osot_force_rows.argtypes = [C.POINTER(ForceModel), C.POINTER(ForceBatch), vp]
+    L.osot_feedback.argtypes = [C.POINTER(FeedbackModel), C.POINTER(FeedbackBatch), vp]
+    L.osot_feedback_state_doubles.argtypes = [C.POINTER(FeedbackModel), ip]
+    L.osot_admittance_params.argtypes = [dp, dp, C.c_double, C.c_double, dp, dp, dp]
     L.osot_computed_torque.argtypes = [C.POINTER(IdModel), vp, vp, vp, C.c_double, vp]
     L.osot_kin_create.argtypes = [C.POINTER(KinDesc), C.c_int, C.POINTER(vp)]
     L.osot_kin_destroy.argtypes = [vp]

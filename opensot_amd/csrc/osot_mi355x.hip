@@ -23,6 +23,7 @@
 #include "osot_ehqp.h"
 #include "osot_id.h"
 #include "osot_force.h"
+#include "osot_feedback.h"
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
 #include "osot_qp_big.h"
@@ -226,6 +227,15 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
         OSOT_F(static_A) OSOT_F(static_A_stride) OSOT_F(static_A_ld) OSOT_F(static_lo) OSOT_F(static_up) OSOT_F(static_b_stride)
         OSOT_F(static_q_tau) OSOT_F(cart_b) OSOT_F(cart_b_stride) OSOT_F(cart_pose_ref) OSOT_F(cart_vel_ref) OSOT_F(cart_f_des)
         OSOT_F(cart_pose_error) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_feedback_model) OSOT_F(nv) OSOT_F(floating_base) OSOT_F(n_cart) OSOT_F(joint) OSOT_F(imu) OSOT_F(n_pairs) OSOT_F(n)
+        OSOT_F(cart_C) OSOT_F(cart_deadzone) OSOT_F(cart_omega) OSOT_F(cart_damping) OSOT_F(cart_ts) OSOT_F(joint_omega) OSOT_F(joint_damping)
+        OSOT_F(joint_ts) OSOT_F(joint_C_scalar) OSOT_F(contact_lambda) OSOT_F(ca_threshold) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_feedback_batch) OSOT_F(B) OSOT_F(state) OSOT_F(cart_pose) OSOT_F(cart_wrench) OSOT_F(cart_wrench_ref)
+        OSOT_F(cart_twist_in) OSOT_F(cart_twist_out) OSOT_F(joint_tau) OSOT_F(joint_h) OSOT_F(joint_C) OSOT_F(joint_qdot_out)
+        OSOT_F(imu_fb_J) OSOT_F(imu_fb_J_stride) OSOT_F(imu_pose) OSOT_F(imu_omega) OSOT_F(imu_A) OSOT_F(imu_A_stride) OSOT_F(imu_A_ld)
+        OSOT_F(imu_b) OSOT_F(imu_b_stride) OSOT_F(contact_pose) OSOT_F(contact_pose_ref) OSOT_F(contact_b_in) OSOT_F(contact_b_in_stride)
+        OSOT_F(contact_b_out) OSOT_F(contact_b_out_stride) OSOT_F(ca_J) OSOT_F(ca_J_stride) OSOT_F(ca_dist) OSOT_F(ca_A) OSOT_F(ca_A_stride)
+        OSOT_F(ca_A_ld) OSOT_F(ca_b) OSOT_F(ca_b_stride) OSOT_LAYOUT_END()
 #undef OSOT_LAYOUT_BEGIN
 #undef OSOT_F
 #undef OSOT_LAYOUT_END
@@ -1548,6 +1558,34 @@ int osot_force_rows(const osot_force_model* m, const osot_force_batch* b, void* 
     if (b->B == 0) return OSOT_OK;
     hipLaunchKernelGGL(osot_force_rows_kernel, dim3((unsigned)b->B), dim3(64), force_lds_bytes(m->n_contacts), (hipStream_t)hip_stream, *m, *b);
     HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// tasks driven by measurements (osot_feedback.h): CartesianAdmittance, JointAdmittance, IMU, the contact error, the collision task
+int osot_feedback(const osot_feedback_model* m, const osot_feedback_batch* b, void* hip_stream) {
+    const char* why = "";
+    const int rc = feedback_check(m, b, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_feedback: ") + why);
+    if (b->B == 0) return OSOT_OK;
+    FeedbackCoeffs k;
+    feedback_coeffs(m, &k);
+    hipLaunchKernelGGL(osot_feedback_kernel, dim3((unsigned)b->B), dim3(64), feedback_lds_bytes(m, b), (hipStream_t)hip_stream, *m, *b, k);
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+int osot_feedback_state_doubles(const osot_feedback_model* m, int* count) {
+    if (!m || !count) return fail(OSOT_ERR_INVALID, "osot_feedback_state_doubles: null argument");
+    if (m->nv < 1 || m->nv > OSOT_KIN_MAX_JOINTS || m->n_cart < 0 || m->n_cart > OSOT_FEEDBACK_MAX_CART || (m->joint != 0 && m->joint != 1))
+        return fail(OSOT_ERR_INVALID, "osot_feedback_state_doubles: nv, n_cart or joint is out of range");
+    *count = feedback_state_count(m);
+    return OSOT_OK;
+}
+
+int osot_admittance_params(const double K[6], const double D[6], double lambda, double dt, double C[6], double M[6], double w[6]) {
+    const char* why = "";
+    const int rc = feedback_admittance_params(K, D, lambda, dt, C, M, w, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_admittance_params: ") + why);
     return OSOT_OK;
 }
 

@@ -1376,18 +1376,51 @@ def _frame_lin_jacobian(model, q, f):
     return p, J
 
 
-def make_base_estimation_stack(B, seed=None, legs=4, leg_joints=2, eps_factor=2e2):
+def _frame_ang_jacobian(model, q, f):
+    """numpy: world rotation R and angular Jacobian [3][n] of frame f at q[n] (the recurrence of _frame_lin_jacobian)"""
+    n = model.n
+    Rw = np.zeros((n, 3, 3))
+    for j in range(n):
+        Rl = model.R0[j]
+        if model.jtype[j] == abi.JOINT_REVOLUTE:
+            x, y, z = model.axis[j]
+            c, s = np.cos(q[j]), np.sin(q[j])
+            K = np.array([[0.0, -z, y], [z, 0.0, -x], [-y, x, 0.0]])
+            Rl = model.R0[j] @ (np.eye(3) + s * K + (1.0 - c) * (K @ K))
+        a = model.parent[j]
+        Rw[j] = Rl if a < 0 else Rw[a] @ Rl
+    _, jf, Rf, _ = model.frames[f]
+    J = np.zeros((3, n))
+    j = jf
+    while j >= 0:
+        if model.jtype[j] == abi.JOINT_REVOLUTE:
+            J[:, j] = Rw[j] @ model.axis[j]
+        j = model.parent[j]
+    return Rw[jf] @ np.asarray(Rf, dtype=float), J
+
+
+def make_base_estimation_stack(B, seed=None, legs=4, leg_joints=2, eps_factor=2e2, imu=False, contact_lambda=0.0):
     """Floating-base estimation after examples/cpp/qp_estimation.cpp: a 6-variable plan whose one level holds a
     tasks::floating_base::Contact per wheel, here a point contact (K = [I 0]: the 3 linear rows) on a frame "contact_<i>" fixed on
     the rim of wheel i; A = (K Ad(R_f') J_f)[:, 0:6] and b = -(K Ad(R_f') J_f)[:, 6:] qdot[6:] are both written by the producer
     (split contact row sets: A into A_0, b into the OSOT_TASK_GENERIC leaves).  The joint velocities qdot[6:] are made consistent with
     a base twist planted in qdot[0:6] -- each leg's three joints carry its contact frame's velocity to zero -- so the least-squares
     residual is zero and the solution is the planted twist.  eps_factor: iHQP's default regularisation (the answer is asked to 1e-9).
-    Returns (plan, leaf, model); leaf["state"] = q0, qdot."""
+    imu=True: a tasks::floating_base::IMU block (6 rows over the six variables: zeros, then the angular rows of the base link's Jacobian;
+    b = [0; R_imu omega], IMU.cpp:33-42) joins the level behind the contacts, as in the example; its rows and b are osot_feedback's.
+    The IMU sits on the base link (frame "base"); the gyroscope reading leaf["state"]["imu_omega"] is the planted twist's angular
+    velocity in the IMU's frame, so the solution stays the planted twist.
+    contact_lambda != 0: the lambda * err term of floating_base::Contact (Contact.cpp:55-66).  err has six entries, so the contacts
+    become full ones (K = I: 6 rows each, as the reference's constructor needs for that term); the producer's b goes to a buffer
+    and osot_feedback adds lambda [p_d - p; -e_o] against leaf["state"]["contact_pose_ref"] [B][legs][12] (all zero: the first
+    posture's poses).  The angular rows are not consistent with the planted twist (the wheels spin): the answer is a least-squares one.
+    Returns (plan, leaf, model); leaf["state"] = q0, qdot (+ contact_rows, imu, imu_omega, contact_lambda, contact_pose_ref, feedback:
+    the feedback.FeedbackModel, where either option is on); bind_base_estimation() wires the device tensors."""
     rng = np.random.default_rng(33000 if seed is None else seed)
     model = make_wheeled_tree(legs, leg_joints)
     n = model.n
-    K = np.eye(6)[:3]
+    K = np.eye(6) if contact_lambda != 0.0 else np.eye(6)[:3]
+    rows = K.shape[0]
     model.frames = model.frames[:1]                       # the base; the wheel centres make room for the contact frames
     for i, w in enumerate(model.wheel_joints):
         model.frames.append((f"contact_{i}", w, np.eye(3), (WHEEL_RADIUS, 0.0, 0.0)))
@@ -1404,10 +1437,19 @@ def make_base_estimation_stack(B, seed=None, legs=4, leg_joints=2, eps_factor=2e
             qdot[i, cols] = sol
             assert np.abs(J @ qdot[i]).max() < 1e-12, "a leg cannot hold its contact still: pick another posture"
     z = lambda *sh: np.zeros(sh)
-    plan = StackPlan(n=6, levels=[[Task(abi.TASK_GENERIC, 3, name=f"contact_{i}") for i in range(legs)]],
-                     eps_abs=eps_abs_from_factor(eps_factor))
-    leaf = {"B": B, "A": [z(B, 3 * legs, 6)], "task": [[(z(B, 3), None, None) for _ in range(legs)]], "bound": [], "rows": [], "C": [],
-            "state": {"q0": q0, "qdot": qdot}}
+    tasks = [Task(abi.TASK_GENERIC, rows, name=f"contact_{i}") for i in range(legs)] + ([Task(abi.TASK_GENERIC, 6, name="imu")] if imu else [])
+    plan = StackPlan(n=6, levels=[tasks], eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, rows * legs + (6 if imu else 0), 6)],
+            "task": [[(z(B, rows), None, None) for _ in range(legs)] + ([(z(B, 6), None, None)] if imu else [])],
+            "bound": [], "rows": [], "C": [], "state": {"q0": q0, "qdot": qdot}}
+    if imu or contact_lambda != 0.0:
+        from .feedback import FeedbackModel
+        omega = np.zeros((B, 3))
+        for i in range(B):
+            R, Jw = _frame_ang_jacobian(model, q0[i], 0)
+            omega[i] = R.T @ (Jw @ qdot[i])
+        leaf["state"].update(contact_rows=rows, imu=bool(imu), imu_omega=omega, contact_lambda=float(contact_lambda),
+                             contact_pose_ref=z(B, legs, 12), feedback=FeedbackModel(n, floating_base=True, imu=imu, contact_lambda=contact_lambda))
     return plan, leaf, model
 
 
@@ -1514,3 +1556,171 @@ def make_wide_force_stack(B, seed=None, nv=64, n_contacts=8, eps_factor=1e6):
                       "quantities": {"pose": pose, "Jc": Jc, "com": rng.uniform(-0.2, 0.2, (B, 3)), "momentum": z(B, 6), "h_gravity": h},
                       "nominal": W0.reshape(B, nf)}}
     return plan, leaf, None
+
+
+# ---- the tasks driven by measurements: references and rows from osot_feedback (opensot_amd/feedback.py) -------------------------------
+def min_joint_vel_task(n, dT, eps=1.0, name="MinJointVel"):
+    """tasks::acceleration::MinJointVel (src/tasks/acceleration/MinJointVel.cpp:6-34) needs no kind of its own: it is an
+    acceleration::Postural with lambda = 0, lambda2 = 1 / dT and zero references, b = -qdot / dT, weighted eps I (setEps).  The leaf is
+    the OSOT_TASK_ACC_POSTURAL one with p0 = [0 ; -qdot], p2 = NULL."""
+    if eps < 0.0:
+        raise ValueError("eps should be positive!")
+    return Task(abi.TASK_ACC_POSTURAL, n, weight=float(eps), lam=0.0, lam2=1.0 / float(dT), name=name)
+
+
+def collision_task_rows(stack, dev, level, block, pair_J, pair_dist):
+    """tasks::velocity::CollisionAvoidance (the task built on the constraint's rows): the `ca` group of feedback.Feedback.bind that writes
+    A = -J and b = err of the violated pairs into block `block` of level `level`, an OSOT_TASK_GENERIC block with one row per pair.
+    pair_J ([B][n_pairs][n], or (tensor, first row)) and pair_dist [B][n_pairs] are what osot_kinematics wrote."""
+    tasks = stack.plan.levels[level]
+    assert tasks[block].kind == abi.TASK_GENERIC
+    return dict(J=pair_J, dist=pair_dist, A=(stack.A[level], sum(t.rows for t in tasks[:block])), b=dev["task"][level][block][0])
+
+
+def make_cartesian_admittance_stack(B, seed=None, tree=None, frame="l_wrist", K=(500.0, 500.0, 500.0, 50.0, 50.0, 50.0), lam=0.01, dt=0.002,
+                                    wall=0.03, stiffness=2000.0, eps_factor=1e6):
+    """`(CartesianAdmittance(l_wrist) / postural) << joint_limits << velocity_limits` on the reference's COMAN: the wrist's pose and
+    Jacobian are left for the kinematics producer, the task's desired twist (leaf p2) for osot_feedback.  The admittance is the
+    constructor's with setImpedanceParams(K, 1.1 K dt / lambda, lambda, dt); the task's lambda is that lambda.  The measured wrench is
+    the caller's: leaf["state"]["wall"] [B][3] is a point `wall` metres from the first posture's wrist for the virtual spring
+    f = stiffness (x_wall - x) the tests and tools drive it with.  Returns (plan, leaf, model, fmodel); bind_cartesian_admittance()
+    wires the device tensors."""
+    from .feedback import FeedbackModel
+    rng = np.random.default_rng(34000 if seed is None else seed)
+    model, q0, qmin, qmax = _coman_bent(rng, B, tree)
+    n = model.n
+    fmodel = FeedbackModel(n, floating_base=True)
+    t = fmodel.add_cartesian_admittance(**FeedbackModel.cartesian_admittance_defaults())
+    K = np.asarray(K, dtype=float)
+    fmodel.set_impedance_params(t, K, 1.1 * K * dt / lam, lam, dt)
+    d = rng.normal(size=(B, 3))
+    z = lambda *sh: np.zeros(sh)
+    levels = [[Task(abi.TASK_CARTESIAN, 6, lam=lam, name="admittance::" + frame)], [Task(abi.TASK_POSTURAL, n, lam=0.01, name="postural")]]
+    bounds = [Bound(abi.BOUND_JOINT_LIMITS, scaling=1.0, name="joint_limits"), Bound(abi.BOUND_VELOCITY_LIMITS, dT=0.05, name="velocity_limits")]
+    plan = StackPlan(n=n, levels=levels, bounds=bounds, eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [z(B, 6, n), None], "task": [[(z(B, 12), z(B, 12), z(B, 6))], [(q0.copy(), q0.copy(), None)]],
+            "bound": [(q0.copy(), np.tile(qmin, (B, 1)), np.tile(qmax, (B, 1))), (np.full((B, n), 2.0), None, None)],
+            "rows": [], "C": [],
+            "state": {"q0": q0, "q_ref": q0.copy(), "frame": frame, "wall": wall * d / np.linalg.norm(d, axis=1, keepdims=True),
+                      "stiffness": stiffness}}
+    return plan, leaf, model, fmodel
+
+
+def bind_cartesian_admittance(stack, kin, fbk, leaf):
+    """wire make_cartesian_admittance_stack to the device: one q tensor is the kinematics producer's input, the Postural task's and the
+    joint limits' q; the producer writes the wrist's pose into the Cartesian task's p0 (= osot_feedback's cart_pose) and its Jacobian
+    into stack.A[0]; osot_feedback (fbk: a feedback.Feedback of the stack's model) writes the task's p2 from `wrench` [B][6], the
+    caller's measurement.  The task's reference pose is the first posture's.  -> (dev_leaf, kin_batch, q, wrench)"""
+    import torch
+    B, s = leaf["B"], leaf["state"]
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q = torch.as_tensor(s["q0"], **f64).contiguous()
+    f = kin.model.frame_index(s["frame"])
+    pose, twist, wrench = torch.zeros((B, 12), **f64), torch.zeros((B, 6), **f64), torch.zeros((B, 6), **f64)
+    kw = dict(frame_pose={f: pose}, frame_J={f: (stack.A[0], 0)})
+    kin.forward(q, **kw)
+    dev["task"][0][0] = (pose, pose.clone(), twist)
+    dev["task"][1][0] = (q, dev["task"][1][0][1], None)
+    dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
+    fbk.bind(cart=[dict(pose=pose, wrench=wrench, twist_out=twist)])
+    return dev, kin.batch_args(q, **kw), q, wrench
+
+
+def make_joint_admittance_stack(B, seed=None, tree=None, inertia=None, dense=False, eps_factor=1e6):
+    """`JointAdmittance << joint_limits << velocity_limits` on the reference's COMAN: one Postural level (lambda = 0.005, the
+    constructor's) whose desired velocity (leaf p2) is osot_feedback's C filter(h - tau), h from osot_dynamics, tau the caller's
+    measurement.  dense: a symmetric positive definite compliance matrix around the constructor's 0.00015 I instead of the scalar.
+    Returns (plan, leaf, model, fmodel); leaf["state"] = q0, q_ref, joint_C ([n][n] or None); bind_joint_admittance() wires the tensors."""
+    import os
+    from . import kinematics as kin
+    from .feedback import FeedbackModel
+    here = os.path.dirname(os.path.abspath(__file__))
+    gold = os.path.join(os.path.dirname(here), "tests", "golden")
+    rng = np.random.default_rng(35000 if seed is None else seed)
+    _, q0, qmin, qmax = _coman_bent(rng, B, tree)
+    model, _, _ = kin.from_json(tree or os.path.join(gold, "coman_tree.json"), inertia or os.path.join(gold, "coman_inertia.json"))
+    n = model.n
+    defaults = FeedbackModel.joint_admittance_defaults()
+    fmodel = FeedbackModel(n, floating_base=True)
+    fmodel.set_joint_admittance(**defaults)
+    Cm = None
+    if dense:
+        G = rng.normal(0.0, 0.1, (n, n))
+        Cm = defaults["C"] * (np.eye(n) + 0.5 * (G + G.T) / n)
+    q_ref = q0.copy()
+    q_ref[:, 6:] += rng.uniform(-0.05, 0.05, (B, n - 6))
+    plan = StackPlan(n=n, levels=[[Task(abi.TASK_POSTURAL, n, lam=defaults["lam"], name="joint_admittance")]],
+                     bounds=[Bound(abi.BOUND_JOINT_LIMITS, scaling=1.0, name="joint_limits"), Bound(abi.BOUND_VELOCITY_LIMITS, dT=0.05, name="velocity_limits")],
+                     eps_abs=eps_abs_from_factor(eps_factor))
+    leaf = {"B": B, "A": [None], "task": [[(q0.copy(), q_ref, np.zeros((B, n)))]],
+            "bound": [(q0.copy(), np.tile(qmin, (B, 1)), np.tile(qmax, (B, 1))), (np.full((B, n), 2.0), None, None)],
+            "rows": [], "C": [], "state": {"q0": q0, "q_ref": q_ref, "joint_C": Cm}}
+    return plan, leaf, model, fmodel
+
+
+def bind_joint_admittance(stack, dyn, fbk, leaf):
+    """wire make_joint_admittance_stack to the device: one q tensor is the dynamics producer's input, the Postural task's and the joint
+    limits' q; osot_dynamics (dyn: a dynamics.Dynamics of the model, at rest) writes h, osot_feedback the task's p2 from h and `tau`
+    [B][n], the caller's measurement.  -> (dev_leaf, dyn_batch, q, tau, h)"""
+    import torch
+    B, s = leaf["B"], leaf["state"]
+    n = stack.plan.n
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q = torch.as_tensor(s["q0"], **f64).contiguous()
+    h, tau, qd = torch.zeros((B, n), **f64), torch.zeros((B, n), **f64), torch.zeros((B, n), **f64)
+    dev["task"][0][0] = (q, dev["task"][0][0][1], qd)
+    dev["bound"][0] = (q,) + tuple(dev["bound"][0][1:])
+    joint = dict(tau=tau, h=h, qdot_out=qd)
+    if s["joint_C"] is not None:
+        joint["C"] = torch.as_tensor(s["joint_C"], **f64).contiguous()
+    fbk.bind(joint=joint)
+    return dev, dyn.batch_args(q, None, h=h), q, tau, h
+
+
+def bind_base_estimation(stack, kin, leaf, fbk=None):
+    """wire make_base_estimation_stack to the device: the producer writes the contacts' A into stack.A[0] and their b into the blocks'
+    leaves -- with contact_lambda != 0 into a buffer of its own, from which osot_feedback (one call per contact: fbks, a list of
+    feedback.Feedback) forms the leaf's b = b_in + lambda err against leaf["state"]["contact_pose_ref"] (zeros: the first posture's
+    contact poses are taken).  With imu=True the base link's Jacobian and pose go to buffers osot_feedback reads, the gyroscope
+    reading is leaf["state"]["imu_omega"], and the IMU block's rows land behind the contacts' in stack.A[0], its b in its leaf.
+    fbk: a feedback.Feedback of leaf["state"]["feedback"], or None to make them here.
+    -> (dev_leaf, kin_batch, q, qdot, fbks): launch every entry of fbks between osot_kinematics and osot_cycle"""
+    import torch
+    from .feedback import Feedback
+    B, s = leaf["B"], leaf["state"]
+    legs, n, rows = len(kin.model.wheel_joints), kin.model.n, s.get("contact_rows", 3)
+    dev = stack.load_leaf(leaf)
+    f64 = dict(dtype=torch.float64, device=stack.device)
+    q, qdot = torch.as_tensor(s["q0"], **f64).contiguous(), torch.as_tensor(s["qdot"], **f64).contiguous()
+    lam, imu = s.get("contact_lambda", 0.0), s.get("imu", False)
+    b_in = torch.zeros((B, 6 * legs), **f64) if lam != 0.0 else None
+    kw = dict(rowset_A={i: (stack.A[0], rows * i) for i in range(legs)}, qdot=qdot,
+              rowset_b={i: ((b_in, 6 * i) if lam != 0.0 else (dev["task"][0][i][0], 0)) for i in range(legs)})
+    fbks = []
+    if lam != 0.0:
+        poses = [torch.zeros((B, 12), **f64) for _ in range(legs)]
+        kw["frame_pose"] = {1 + i: poses[i] for i in range(legs)}
+    if imu:
+        base_pose, base_J = torch.zeros((B, 12), **f64), torch.zeros((B, 6, n), **f64)
+        kw.setdefault("frame_pose", {})[0] = base_pose
+        kw["frame_J"] = {0: (base_J, 0)}
+    kin.forward(q, **kw)
+    if lam != 0.0:
+        ref = torch.as_tensor(s["contact_pose_ref"], **f64).contiguous()
+        for i in range(legs):
+            if not np.any(s["contact_pose_ref"][:, i]):
+                ref[:, i] = poses[i]
+    for i in range(legs if lam != 0.0 else 0):
+        f = Feedback(s["feedback"], B, stack.device) if (fbk is None or i > 0) else fbk
+        f.bind(contact=dict(pose=poses[i], pose_ref=ref[:, i].contiguous(), b_in=(b_in, 6 * i), b_out=dev["task"][0][i][0]),
+               imu=dict(fb_J=base_J, pose=base_pose, omega=torch.as_tensor(s["imu_omega"], **f64).contiguous(),
+                        A=(stack.A[0], rows * legs), b=dev["task"][0][legs][0]) if (imu and i == 0) else None)
+        fbks.append(f)
+    if imu and lam == 0.0:
+        f = Feedback(s["feedback"], B, stack.device) if fbk is None else fbk
+        f.bind(imu=dict(fb_J=base_J, pose=base_pose, omega=torch.as_tensor(s["imu_omega"], **f64).contiguous(),
+                        A=(stack.A[0], rows * legs), b=dev["task"][0][legs][0]))
+        fbks.append(f)
+    return dev, kin.batch_args(q, **kw), q, qdot, fbks
