@@ -1207,6 +1207,102 @@ int osot_feedback_state_doubles(const osot_feedback_model* model, int* count);
  * D[i] <= K[i] dt / lambda for some i (nothing is written), or an argument is NULL. */
 int osot_admittance_params(const double K[6], const double D[6], double lambda, double dt, double C[6], double M[6], double w[6]);
 
+/* ---- acceleration task leaves: tracking errors, gain matrices and GainType::Force --------------------------------------
+ * osot_acc_tasks turns the model quantities osot_kinematics / osot_dynamics leave on the device into the leaf arrays of the
+ * acceleration kinds above (no plan kind is added).  It is a launch of its own between osot_dynamics and osot_id_rows:
+ *     osot_kinematics -> osot_dynamics -> osot_acc_tasks -> osot_id_rows -> osot_cycle -> osot_computed_torque
+ *   acceleration::Cartesian (src/tasks/acceleration/Cartesian.cpp:147-169), per term t < n_cart, into the leaf p0 of an
+ *   OSOT_TASK_ACC_CARTESIAN block (a SubTask is the plan's business: the leaf has the parent's six rows):
+ *       pose_err = [p_ref - p; cart_orientation_gain * e_o], e_o = -2 x the quaternion error of
+ *                  include/OpenSoT/utils/cartesian_utils.h:144-164 on the short path, from the actual to the reference orientation
+ *                  (the convention of force::Cartesian above).  XBot::Utils::computeOrientationError is not vendored: parity with
+ *                  it is unpinned, as for every model quantity here.  The update kernel does not apply an orientation gain to a
+ *                  supplied pose_err: it is applied here.
+ *       vel_err  = vel_ref - J qdot
+ *       cart_p0  = [pose_err; vel_err]            (12) without gain matrices and with the Acceleration type
+ *                  [pose_err; vel_err; Gp; Gd]    (84) with cart_gain_matrices or the Force type: what acc_gain_matrices reads.
+ *                  Acceleration type: Gp = Kp, Gd = Kd.  Force type (:161-169, 517-524): Gp = Mi Kp, Gd = Mi Kd, Mi = J M^-1 J'.
+ *       cart_a_ref_out = cart_a_ref_in + Mi cart_f_virtual (Force type; otherwise a copy): the leaf p2 (p1 is Jdot qdot,
+ *                  osot_dynamics').
+ *   acceleration::CoM (CoM.cpp:74-97; it has no Force type): com_p0 = [com_ref - com; vel_ref - J_com qdot], behind them Kp and
+ *       Kd (3 x 3 each) with com_gain_matrices.
+ *   acceleration::Postural (Postural.cpp:135-163): post_p0 = [q_ref - q; qdot_ref - qdot] always, and
+ *       post_qddot_out = qddot_ref + G (post_lambda2 Kd vel_err + post_lambda Kp pos_err), G = I (Acceleration) or M^-1 (Force).
+ *       A stack with matrix gains or the Force type binds post_qddot_out as the block's p2 and sets the plan's lambda = lambda2 = 0
+ *       on that block (the update then gives b = p2); with scalar gains and the Acceleration type it need not be bound.
+ *   Minv: computeInertiaInverse, [nv][nv], exactly symmetric.
+ * M = L L' is factored once per instance; Mi, M^-1 v and Minv all come from that factor by triangular solves (no inverse is
+ * formed for the tasks).  Only the lower triangle of M is read, and only when a term is Force-type or Minv is bound.  A pivot
+ * that is not finite or not above (nv + 1) 2^-52 x the largest diagonal entry of M counts as failed: ok = 0 for that instance,
+ * its Force-type Gp, Gd, Mi and its Minv are written as zeros, cart_a_ref_out = cart_a_ref_in, post_qddot_out = qddot_ref (Force
+ * type), its other outputs as usual; no NaN or Inf is written and the other instances are not affected. */
+#define OSOT_ACC_MAX_CART 8
+#define OSOT_ACC_GAIN_ACCELERATION 0
+#define OSOT_ACC_GAIN_FORCE 1
+typedef struct {
+    int nv;                                       /* coordinates of the tree, 1 .. OSOT_KIN_MAX_JOINTS                       */
+    int n_cart;                                   /* Cartesian terms, 0 .. OSOT_ACC_MAX_CART                                 */
+    int cart_gain_type[OSOT_ACC_MAX_CART];        /* OSOT_ACC_GAIN_ACCELERATION / OSOT_ACC_GAIN_FORCE                        */
+    int cart_gain_matrices[OSOT_ACC_MAX_CART];    /* 0 / 1: Kp, Kd are written behind the errors (implied by the Force type) */
+    double cart_Kp[OSOT_ACC_MAX_CART * 36];       /* [t] row-major 6 x 6 (the reference's default: the identity)             */
+    double cart_Kd[OSOT_ACC_MAX_CART * 36];
+    double cart_orientation_gain[OSOT_ACC_MAX_CART];
+    int has_com;                                  /* 0 / 1                                                                   */
+    int com_gain_matrices;                        /* 0 / 1                                                                   */
+    double com_Kp[9], com_Kd[9];                  /* row-major 3 x 3                                                         */
+    int has_postural;                             /* 0 / 1                                                                   */
+    int post_gain_type;
+    int post_gain_matrices;                       /* 0 / 1: post_Kp / post_Kd are read (0: they must be NULL)                */
+    double post_lambda, post_lambda2;
+    const double* post_Kp;                        /* DEVICE [nv][nv] row-major, one for the batch; NULL = the identity       */
+    const double* post_Kd;
+} osot_acc_model;
+typedef struct {
+    int B;
+    const double* q;                                   /* [B][nv] (read by the postural term)                                */
+    const double* qdot;                                /* [B][nv]                                                            */
+    const double* M;                                   /* first element of instance 0, as osot_dyn_batch.M writes it         */
+    long long M_stride;                                /* doubles from one instance to the next (>= nv * nv)                 */
+    const double* cart_J[OSOT_ACC_MAX_CART];           /* first of the 6 rows of term t in instance 0; may point into A_k or
+                                                          Jc, where osot_kinematics wrote it                                 */
+    long long cart_J_stride[OSOT_ACC_MAX_CART];        /* doubles from one instance to the next (>= 6 ld)                    */
+    int cart_J_ld[OSOT_ACC_MAX_CART];                  /* row length in doubles (>= nv); columns nv .. ld-1 are not read     */
+    const double* cart_pose[OSOT_ACC_MAX_CART];        /* [B][12] as osot_kinematics writes it (R row-major; p)              */
+    const double* cart_pose_ref[OSOT_ACC_MAX_CART];    /* [B][12]                                                            */
+    const double* cart_vel_ref[OSOT_ACC_MAX_CART];     /* [B][6]; NULL = zero                                                */
+    const double* cart_f_virtual[OSOT_ACC_MAX_CART];   /* [B][6]; NULL = zero (Force type only)                              */
+    const double* cart_a_ref_in[OSOT_ACC_MAX_CART];    /* [B][6]; NULL = zero                                                */
+    double* cart_p0[OSOT_ACC_MAX_CART];                /* 12 or 84 doubles per instance, or NULL                             */
+    long long cart_p0_stride[OSOT_ACC_MAX_CART];
+    double* cart_a_ref_out[OSOT_ACC_MAX_CART];         /* [B][6] or NULL                                                     */
+    double* cart_Mi[OSOT_ACC_MAX_CART];                /* [B][36] or NULL (Force type only)                                  */
+    const double* com_J;                               /* first of the 3 rows in instance 0                                  */
+    long long com_J_stride;                            /* (>= 3 ld)                                                          */
+    int com_J_ld;                                      /* (>= nv)                                                            */
+    const double* com;                                 /* [B][3]                                                             */
+    const double* com_ref;                             /* [B][3]                                                             */
+    const double* com_vel_ref;                         /* [B][3]; NULL = zero                                                */
+    double* com_p0;                                    /* 6 or 24 doubles per instance, or NULL                              */
+    long long com_p0_stride;
+    const double* post_q_ref;                          /* [B][nv]                                                            */
+    const double* post_qdot_ref;                       /* [B][nv]; NULL = zero                                               */
+    const double* post_qddot_ref;                      /* [B][nv]; NULL = zero                                               */
+    double* post_p0;                                   /* [B][2 nv] or NULL                                                  */
+    double* post_qddot_out;                            /* [B][nv] or NULL                                                    */
+    double* Minv;                                      /* first element of instance 0, or NULL                               */
+    long long Minv_stride;                             /* (>= nv * nv)                                                       */
+    int* ok;                                           /* [B] or NULL: 1 = the factorisation ran through (or was not needed) */
+} osot_acc_batch;
+/* Stream-ordered, no allocation, capturable; B == 0 is a no-op.  (The first launch on a device that needs more than 64 KB of LDS
+ * -- nv near 64 with many terms or Minv -- raises the kernel's limit, a host-side setting made once; make that launch before a
+ * capture.)  Refused with OSOT_ERR_INVALID before any device is touched
+ * (osot_last_error() names the field): a size out of range, an unknown gain type, a flag that is not 0 / 1, a non-finite gain,
+ * M NULL when it is needed, a required input that is NULL, a stride or row length below what the rows need, an output that
+ * aliases an input of its term, a pointer bound to a term beyond n_cart or to a group the model lacks, post_Kp / post_Kd with
+ * post_gain_matrices == 0, cart_Mi or cart_f_virtual on a term that is not Force-type, a reference without its output.  nv > 64: OSOT_ERR_UNSUPPORTED (beyond it the
+ * Force-type gains are osot_id_force_gains' with an inverse inertia matrix of the caller's). */
+int osot_acc_tasks(const osot_acc_model* model, const osot_acc_batch* batch, void* hip_stream);
+
 /* ---- layout of the structs above as THIS library was compiled (for bindings that mirror them by hand: ctypes, cgo, JNI ...).
  * name = the typedef's name ("osot_plan_desc", "osot_qp_batch", ...).  *size = sizeof; the byte offset of every member, in
  * declaration order, goes to offsets[0 .. *n_fields) (at most max_fields are written; offsets may be NULL).  Unknown name:

@@ -262,13 +262,42 @@ class FeedbackBatch(C.Structure):
                 ("ca_b", C.c_void_p), ("ca_b_stride", C.c_longlong)]
 
 
+ACC_MAX_CART = 8
+ACC_GAIN_ACCELERATION, ACC_GAIN_FORCE = 0, 1
+
+
+class AccModel(C.Structure):
+    _fields_ = [("nv", C.c_int), ("n_cart", C.c_int), ("cart_gain_type", C.c_int * ACC_MAX_CART),
+                ("cart_gain_matrices", C.c_int * ACC_MAX_CART), ("cart_Kp", C.c_double * (36 * ACC_MAX_CART)),
+                ("cart_Kd", C.c_double * (36 * ACC_MAX_CART)), ("cart_orientation_gain", C.c_double * ACC_MAX_CART),
+                ("has_com", C.c_int), ("com_gain_matrices", C.c_int), ("com_Kp", C.c_double * 9), ("com_Kd", C.c_double * 9),
+                ("has_postural", C.c_int), ("post_gain_type", C.c_int), ("post_gain_matrices", C.c_int),
+                ("post_lambda", C.c_double), ("post_lambda2", C.c_double), ("post_Kp", C.c_void_p), ("post_Kd", C.c_void_p)]
+
+
+class AccBatch(C.Structure):
+    _fields_ = [("B", C.c_int), ("q", C.c_void_p), ("qdot", C.c_void_p), ("M", C.c_void_p), ("M_stride", C.c_longlong),
+                ("cart_J", C.c_void_p * ACC_MAX_CART), ("cart_J_stride", C.c_longlong * ACC_MAX_CART), ("cart_J_ld", C.c_int * ACC_MAX_CART),
+                ("cart_pose", C.c_void_p * ACC_MAX_CART), ("cart_pose_ref", C.c_void_p * ACC_MAX_CART),
+                ("cart_vel_ref", C.c_void_p * ACC_MAX_CART), ("cart_f_virtual", C.c_void_p * ACC_MAX_CART),
+                ("cart_a_ref_in", C.c_void_p * ACC_MAX_CART), ("cart_p0", C.c_void_p * ACC_MAX_CART),
+                ("cart_p0_stride", C.c_longlong * ACC_MAX_CART), ("cart_a_ref_out", C.c_void_p * ACC_MAX_CART),
+                ("cart_Mi", C.c_void_p * ACC_MAX_CART),
+                ("com_J", C.c_void_p), ("com_J_stride", C.c_longlong), ("com_J_ld", C.c_int),
+                ("com", C.c_void_p), ("com_ref", C.c_void_p), ("com_vel_ref", C.c_void_p),
+                ("com_p0", C.c_void_p), ("com_p0_stride", C.c_longlong),
+                ("post_q_ref", C.c_void_p), ("post_qdot_ref", C.c_void_p), ("post_qddot_ref", C.c_void_p),
+                ("post_p0", C.c_void_p), ("post_qddot_out", C.c_void_p),
+                ("Minv", C.c_void_p), ("Minv_stride", C.c_longlong), ("ok", C.c_void_p)]
+
+
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
     "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
     "osot_plan_stored_constraint_rows",
     "osot_solver_create", "osot_solver_destroy", "osot_stack_update", "osot_ihqp_solve", "osot_cycle", "osot_nhqp_solve", "osot_ehqp_solve",
     "osot_solver_kernel_time_ms", "osot_solver_set_timing", "osot_solver_set_schedule", "osot_solver_set_hotstart", "osot_solver_set_specialisation", "osot_solver_set_task_active", "osot_solver_resident_waves", "osot_solver_resident_waves_nhqp",
-    "osot_id_rows", "osot_force_rows", "osot_feedback", "osot_feedback_state_doubles", "osot_admittance_params", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_pure_rolling_s33", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
+    "osot_id_rows", "osot_force_rows", "osot_acc_tasks", "osot_feedback", "osot_feedback_state_doubles", "osot_admittance_params", "osot_id_force_gains", "osot_computed_torque", "osot_kin_create", "osot_kin_destroy", "osot_kinematics", "osot_pure_rolling_s33", "osot_shape_distance", "osot_dyn_create", "osot_dyn_destroy", "osot_dynamics",
     "osot_grad_create", "osot_grad_destroy", "osot_posture_gradient", "osot_control_cycle", "osot_control_rollout", "osot_solver_profile_phases",
     "osot_backend_create", "osot_backend_destroy", "osot_backend_init_problem",
     "osot_backend_update_task", "osot_backend_update_constraints", "osot_backend_update_bounds",
@@ -289,7 +318,8 @@ STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound
            "osot_admm_options": AdmmOptions, "osot_id_model": IdModel, "osot_kin_desc": KinDesc, "osot_kin_batch": KinBatch,
            "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch, "osot_shape": Shape,
            "osot_force_model": ForceModel, "osot_force_batch": ForceBatch,
-           "osot_feedback_model": FeedbackModel, "osot_feedback_batch": FeedbackBatch}
+           "osot_feedback_model": FeedbackModel, "osot_feedback_batch": FeedbackBatch,
+           "osot_acc_model": AccModel, "osot_acc_batch": AccBatch}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -346,6 +376,7 @@ def lib():
     L.osot_id_rows.argtypes = [C.POINTER(IdModel), vp, C.c_longlong, vp, C.c_longlong, C.c_int, vp, vp, vp, vp, vp]
     L.osot_force_rows.argtypes = [C.POINTER(ForceModel), C.POINTER(ForceBatch), vp]
     L.osot_feedback.argtypes = [C.POINTER(FeedbackModel), C.POINTER(FeedbackBatch), vp]
+    L.osot_acc_tasks.argtypes = [C.POINTER(AccModel), C.POINTER(AccBatch), vp]
     L.osot_feedback_state_doubles.argtypes = [C.POINTER(FeedbackModel), ip]
     L.osot_admittance_params.argtypes = [dp, dp, C.c_double, C.c_double, dp, dp, dp]
     L.osot_computed_torque.argtypes = [C.POINTER(IdModel), vp, vp, vp, C.c_double, vp]

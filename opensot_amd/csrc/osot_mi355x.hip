@@ -24,6 +24,7 @@
 #include "osot_id.h"
 #include "osot_force.h"
 #include "osot_feedback.h"
+#include "osot_acc.h"
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
 #include "osot_qp_big.h"
@@ -236,6 +237,14 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
         OSOT_F(imu_b) OSOT_F(imu_b_stride) OSOT_F(contact_pose) OSOT_F(contact_pose_ref) OSOT_F(contact_b_in) OSOT_F(contact_b_in_stride)
         OSOT_F(contact_b_out) OSOT_F(contact_b_out_stride) OSOT_F(ca_J) OSOT_F(ca_J_stride) OSOT_F(ca_dist) OSOT_F(ca_A) OSOT_F(ca_A_stride)
         OSOT_F(ca_A_ld) OSOT_F(ca_b) OSOT_F(ca_b_stride) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_acc_model) OSOT_F(nv) OSOT_F(n_cart) OSOT_F(cart_gain_type) OSOT_F(cart_gain_matrices) OSOT_F(cart_Kp) OSOT_F(cart_Kd)
+        OSOT_F(cart_orientation_gain) OSOT_F(has_com) OSOT_F(com_gain_matrices) OSOT_F(com_Kp) OSOT_F(com_Kd) OSOT_F(has_postural)
+        OSOT_F(post_gain_type) OSOT_F(post_gain_matrices) OSOT_F(post_lambda) OSOT_F(post_lambda2) OSOT_F(post_Kp) OSOT_F(post_Kd) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_acc_batch) OSOT_F(B) OSOT_F(q) OSOT_F(qdot) OSOT_F(M) OSOT_F(M_stride) OSOT_F(cart_J) OSOT_F(cart_J_stride)
+        OSOT_F(cart_J_ld) OSOT_F(cart_pose) OSOT_F(cart_pose_ref) OSOT_F(cart_vel_ref) OSOT_F(cart_f_virtual) OSOT_F(cart_a_ref_in)
+        OSOT_F(cart_p0) OSOT_F(cart_p0_stride) OSOT_F(cart_a_ref_out) OSOT_F(cart_Mi) OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(com_J_ld)
+        OSOT_F(com) OSOT_F(com_ref) OSOT_F(com_vel_ref) OSOT_F(com_p0) OSOT_F(com_p0_stride) OSOT_F(post_q_ref) OSOT_F(post_qdot_ref)
+        OSOT_F(post_qddot_ref) OSOT_F(post_p0) OSOT_F(post_qddot_out) OSOT_F(Minv) OSOT_F(Minv_stride) OSOT_F(ok) OSOT_LAYOUT_END()
 #undef OSOT_LAYOUT_BEGIN
 #undef OSOT_F
 #undef OSOT_LAYOUT_END
@@ -1570,6 +1579,31 @@ int osot_feedback(const osot_feedback_model* m, const osot_feedback_batch* b, vo
     FeedbackCoeffs k;
     feedback_coeffs(m, &k);
     hipLaunchKernelGGL(osot_feedback_kernel, dim3((unsigned)b->B), dim3(64), feedback_lds_bytes(m, b), (hipStream_t)hip_stream, *m, *b, k);
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// acceleration task leaves (osot_acc.h): acceleration::Cartesian / CoM / Postural with gain matrices and GainType::Force, Minv
+int osot_acc_tasks(const osot_acc_model* m, const osot_acc_batch* b, void* hip_stream) {
+    const char* why = "";
+    int rc = acc_check(m, b, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_acc_tasks: ") + why);
+    if (b->B == 0) return OSOT_OK;
+    const size_t lds = (size_t)acc_lds_bytes(m, b);   // 1.5 KB at nv = 7 with one term, 71 KB at nv = 64 with eight and Minv
+    if (lds > 64 * 1024) {
+        // the limit is raised to the largest slice there is, ONCE per device: later launches, captured ones included, only launch
+        static unsigned long long raised = 0ull;     // bit d: done on device d (benign if two threads both do it)
+        int device = 0;
+        HIP_TRY(hipGetDevice(&device));
+        if (device < 0 || device >= 64 || !((raised >> device) & 1ull)) {
+            rc = ensure_lds(osot_acc_tasks_kernel, (size_t)acc_lds_bytes_max());
+            if (rc != OSOT_OK) return rc;
+            if (device >= 0 && device < 64) raised |= 1ull << device;
+        }
+    }
+    AccArgs A;
+    A.M = *m; A.Bt = *b;
+    hipLaunchKernelGGL(osot_acc_tasks_kernel, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, A);
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

@@ -271,6 +271,79 @@ class IdMomentumStep(IdStep):
                          frame_jdotqdot={self.frames[0]: self.jdq_l, self.frames[1]: self.jdq_r}, com_jdotqdot=self.jdq_com, **self._extra)
 
 
+class IdTrackingStep(IdStep):
+    """IdStep for a stack made by synth.make_coman_id_tracking_stack:
+        q, qdot -> osot_kinematics + osot_dynamics -> osot_acc_tasks -> osot_id_rows -> osot_cycle -> osot_computed_torque -> integrate
+    consume() calls osot_acc_tasks (acceleration.AccTasks) in place of IdStep's torch expressions: the CoM errors, the hand's pose and
+    velocity errors with their gain matrices (GainType::Force: Mi Kp, Mi Kd and a_ref + Mi f from a Cholesky factor of model.Bm; no
+    inverse inertia matrix is asked of the host), the postural errors and qddot_d.  The hand's reference pose starts at
+    `offset` from its first pose and moves with vel_ref (hand_ref, hand_vel_ref: the caller's to rewrite)."""
+
+    def __init__(self, plan, leaf, kin_model, device=0, dt=1.0e-3, gravity=(0.0, 0.0, -9.81)):
+        from .acceleration import AccModel, AccTasks
+        super().__init__(plan, leaf, kin_model, device, dt, gravity)
+        B, nv, d = self.B, self.nv, self.st.device
+        t = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.float64).to(d)
+        z = lambda *s: torch.zeros(s, dtype=torch.float64, device=d)
+        tr = leaf["state"]["tracking"]
+        self.hand = kin_model.frame_index(tr["hand"])
+        self.p0_hand, self.jdq_hand, self.a_ref_hand = self.dev["task"][1][0]
+        self.qddot_d = self.dev["task"][2][0][2]
+        self.Jhand, self.hand_pose, self.hand_ref, self.hand_vel_ref = z(B, 6, nv), z(B, 12), z(B, 12), t(tr["vel_ref"])
+        self._offset = t(tr["offset"])
+        self.f_virtual = t(tr["f_virtual"]) if tr["f_virtual"] is not None else None
+        self.com_ref = z(B, 3)
+        self._refs_set = False
+        self.acc_ok = torch.zeros((B,), dtype=torch.int32, device=d)
+        am = AccModel(nv, cart=[dict(gain_type=tr["gain_type"], gain_matrices=True, Kp=tr["Kp"], Kd=tr["Kd"], orientation_gain=tr["orientation_gain"])],
+                      com=dict(gain_matrices=False),
+                      postural=dict(gain_type=tr["gain_type"], gain_matrices=True, lam=tr["post_lam"], lam2=tr["post_lam2"], Kp=tr["post_Kp"], Kd=tr["post_Kd"]),
+                      device=device)
+        self.acc = AccTasks(am)
+        # what the step binds (acc_args: for a caller who wants the same batch with more outputs, e.g. Minv=)
+        self.acc_args = dict(
+            q=self.q, qdot=self.qdot, M=self.model.Bm,
+            cart=[dict(J=self.Jhand, pose=self.hand_pose, pose_ref=self.hand_ref, vel_ref=self.hand_vel_ref, f_virtual=self.f_virtual,
+                       p0=self.p0_hand, a_ref_out=self.a_ref_hand)],
+            com=dict(J=self.Jcom, com=self.com, com_ref=self.com_ref, p0=self.p0_com),
+            postural=dict(q_ref=self.q_ref, p0=self.p0_post, qddot_out=self.qddot_d), ok=self.acc_ok)
+        self._ab = self.acc.batch_args(B, **self.acc_args)
+
+    def produce(self):
+        frames = {f: self.model.contact_rows(c) for c, f in enumerate(self.frames)}
+        frames[self.hand] = (self.Jhand, 0)
+        self.kin.forward(self.q, frame_pose={self.hand: self.hand_pose}, frame_J=frames, com=self.com, com_J=(self.Jcom, 0))
+        self.dyn.forward(self.q, self.qdot, M=self.model.Bm, h=self.model.h,
+                         frame_jdotqdot={self.frames[0]: self.jdq_l, self.frames[1]: self.jdq_r, self.hand: self.jdq_hand},
+                         com_jdotqdot=self.jdq_com)
+
+    def consume(self):
+        if not self._refs_set:                          # the first CoM and the hand's first pose (host-side flag: set before a capture)
+            self.com_ref.copy_(self.com)
+            self.hand_ref.copy_(self.hand_pose)
+            self.hand_ref[:, 9:12].add_(self._offset)
+            self._refs_set = True
+        self.acc.forward(self._ab)
+        self.solve()
+
+    def solve(self):
+        """everything behind the leaves: reads only what the producers and osot_acc_tasks wrote (a caller may fill the leaves
+        p0_com, p0_hand, a_ref_hand, p0_post, qddot_d from another source instead).  Apart from the hand's rows in write_rows this
+        is the tail of IdStep.consume, restated here because IdStep keeps its consume() in one piece: a change to either goes
+        to both."""
+        self.h_u.copy_(self.model.h[:, :6])
+        self.model.write_rows(self.st, dyn_block=0, tau_block=3, tasks=[(0, 0, self.J12), (0, 12, self.Jcom), (1, 0, self.Jhand)])
+        self.st.cycle(self.dev)
+        x = self.st.dq[:self.B]
+        stream = C.c_void_p(torch.cuda.current_stream(self.st.device).cuda_stream)
+        abi.check(self._lib.osot_computed_torque(C.byref(self._mc), C.c_void_p(x.data_ptr()), C.c_void_p(self.tau.data_ptr()),
+                                                 C.c_void_p(self.ok.data_ptr()), 10e-3, stream), "osot_computed_torque")
+
+    def integrate(self):
+        super().integrate()
+        self.hand_ref[:, 9:12].add_(self.hand_vel_ref[:, :3], alpha=self.dt)     # the reference moves with its twist
+
+
 def force_gains(J, Bi, Kp, Kd, p0, rows, f_virtual=None, a_ref=None):
     """GainType::Force of acceleration::Cartesian (src/tasks/acceleration/Cartesian.cpp:161-169): Mi = J Bi J' per instance
     (compute_cartesian_inertia_inverse, :517-524), Gp = Mi Kp and Gd = Mi Kd written into the task's leaf array

@@ -713,6 +713,47 @@ def make_coman_id_stack(B, seed=None, tree=None, inertia=None, eps_factor=1e6):
     return plan, leaf, model
 
 
+def make_coman_id_tracking_stack(B, gain_type=abi.ACC_GAIN_ACCELERATION, seed=None, tree=None, inertia=None, hand="l_wrist", eps_factor=1e6):
+    """make_coman_id_stack with TRACKING tasks whose leaves osot_acc_tasks writes (opensot_amd.dynamics.IdTrackingStep), n = 47:
+
+    levels : 0 = acceleration::Contact on l_sole and r_sole (6 rows each) + acceleration::CoM (3), as in make_coman_id_stack
+             1 = acceleration::Cartesian on `hand` (6 rows) with Kp, Kd MATRICES, following a reference pose that moves with a
+                 reference twist; with gain_type = abi.ACC_GAIN_FORCE the gains are Mi Kp, Mi Kd (GainType::Force) and a virtual
+                 force enters as a_ref + Mi f
+             2 = acceleration::Postural with matrix gains (Force variant: M^-1 in front of them): the producer's qddot_d is the
+                 block's p2, the plan's lambda = lambda2 = 0 on it
+    rows   : as make_coman_id_stack
+    leaf["state"]["tracking"]: hand (frame name), gain_type, Kp, Kd (6 x 6), orientation_gain, offset [B][3] (the reference starts that
+    far from the hand's first pose), vel_ref [B][6] (towards the hand: the reference and the hand meet), f_virtual [B][6] or None,
+    post_Kp / post_Kd (nv x nv), post_lam / post_lam2.  Returns (plan, leaf, model)."""
+    plan0, leaf, model = make_coman_id_stack(B, seed=seed, tree=tree, inertia=inertia, eps_factor=eps_factor)
+    rng = np.random.default_rng(9100 if seed is None else seed + 100)
+    nv, n = model.n, plan0.n
+    force = gain_type == abi.ACC_GAIN_FORCE
+    z = lambda *sh: np.zeros(sh)
+    S = rng.uniform(-1.0, 1.0, (6, 6))
+    # Acceleration type: Kp in 1 / s^2.  Force type: a stiffness in N / m in front of Mi, which at the wrist is the inverse of a few
+    # hundredths of a kilogram (Mi Kp comes to about 200 / s^2: the explicit 1 ms integration of IdStep stays far from its limit)
+    Kp = (10.0 if force else 100.0) * (np.eye(6) + 0.05 * (S + S.T))
+    Kd = (1.0 if force else 20.0) * np.eye(6)
+    offset = rng.uniform(0.01, 0.02, (B, 3)) * rng.choice([-1.0, 1.0], (B, 3))
+    vel_ref = np.concatenate([-0.5 * offset, z(B, 3)], axis=1)
+    d = rng.uniform(0.8, 1.2, nv)
+    post_Kp, post_Kd = (0.2 if force else 25.0) * np.diag(d), (0.04 if force else 10.0) * np.diag(d)
+    levels = [plan0.levels[0],
+              [Task(abi.TASK_ACC_CARTESIAN, 6, lam=1.0, lam2=1.0, orientation_gain=1.0, name=hand, acc_gain_matrices=True)],
+              [Task(abi.TASK_ACC_POSTURAL, nv, lam=0.0, lam2=0.0, name="postural")]]
+    plan = StackPlan(n=n, levels=levels, bounds=[], rowblocks=plan0.rowblocks, eps_abs=plan0.eps_abs)
+    leaf = dict(leaf)
+    leaf["A"] = [leaf["A"][0], z(B, 6, n), None]
+    leaf["task"] = [leaf["task"][0], [(z(B, 84), z(B, 6), z(B, 6))], [(z(B, 2 * nv), None, z(B, nv))]]
+    leaf["state"] = dict(leaf["state"], tracking=dict(
+        hand=hand, gain_type=int(gain_type), Kp=Kp, Kd=Kd, orientation_gain=1.0, offset=offset, vel_ref=vel_ref,
+        f_virtual=np.tile(np.array([0.0, 0.0, 0.1, 0.0, 0.0, 0.0]), (B, 1)) if force else None,
+        post_Kp=post_Kp, post_Kd=post_Kd, post_lam=1.0, post_lam2=1.0))
+    return plan, leaf, model
+
+
 # the sole rectangle around a sole frame's origin (x_l, x_u, y_l, y_u): the CoP limits of make_coman_id_stack, and the corners of the
 # support polygon of make_coman_balance_stack
 SOLE_RECTANGLE = (-0.06, 0.12, -0.045, 0.045)
