@@ -1303,6 +1303,50 @@ typedef struct {
  * Force-type gains are osot_id_force_gains' with an inverse inertia matrix of the caller's). */
 int osot_acc_tasks(const osot_acc_model* model, const osot_acc_batch* batch, void* hip_stream);
 
+/* ---- multipliers, active set and the backward pass of the batched explicit QP (opensot_amd/csrc/osot_qp_sens.h) ---------------
+ * What QPOasesBackEnd keeps of every solve besides x: the dual solution (getDualSolution, QPOasesBackEnd.cpp:153-158, 291-296:
+ * nV + nC entries, the bounds first) and the working set (getActiveBounds / getActiveConstraints, QPOasesBackEnd.h:163-172) --
+ * recovered from the problem and a solution x, for B instances -- and, given grad_x = d loss / d x, the gradients of the loss
+ * with respect to every input of the QP.  Per instance, with H~ = H + eps_abs I (only the LOWER triangle of H is read):
+ *   candidates ... every equality (lA[r] == uA[r], l[i] == u[i]) and every finite side of a bound or row whose residual is within
+ *                  active_tol max(1, |bound|); |v| >= 1e20 counts as absent.  At most 2n, in the order equalities (bounds, rows),
+ *                  bounds, rows: an instance with more is DEGENERATE and processed on the first 2n.
+ *   multipliers .. H~ x + g + C' lambda = 0 in the least-squares sense, by a column-pivoted Householder QR of L^-1 C' (H~ = L L').
+ *                  A column whose pivot is below rank_tol times the first pivot is dependent and leaves the set (DEGENERATE).
+ *                  An inequality with |lambda| <= dual_tol max(1, |lambda|_inf), or with the wrong sign, leaves the set and the
+ *                  factorisation is redone once (DEGENERATE).
+ *   y ............ qpOASES' convention, y = -lambda:  H~ x + g = y_b + A' y_c;  y > 0 on a lower side, y < 0 on an upper side;
+ *                  [B][n + nc], the n bounds first.  active: 0, -1 lower, +1 upper, 2 equality, for the members of the final set.
+ *   backward ..... [H~ C'; C 0] [dx; dlambda] = -[grad_x; 0]:  grad_g = dx, grad_H = (dx x' + x dx') / 2 (symmetric, written in
+ *                  full), grad_A = dlambda_r x' + lambda_r dx' on the rows of the set (written in full, zeros elsewhere),
+ *                  grad_lA / grad_uA / grad_l / grad_u = -dlambda on the side that is active (an equality: on the lower side, zero
+ *                  on the upper: the sum over both is the derivative of a bound moved as one).  No gradient for eps_abs.
+ * An instance whose status is not OSOT_STATUS_SOLVED, whose x is not finite, whose H~ is not positive definite (the pivot rule of
+ * osot_acc_tasks) or whose results are not finite is SKIPPED: every output of it is zero.  Nothing non-finite is written. */
+#define OSOT_SENS_OK         0   /* unique multipliers and derivative                                      */
+#define OSOT_SENS_DEGENERATE 1   /* weakly active, dependent or > 2n candidates: a valid one-sided answer  */
+#define OSOT_SENS_SKIPPED    2   /* status != SOLVED, non-finite x, or H + eps I not PD: all outputs zero   */
+typedef struct osot_qp_sens_options { double active_tol, dual_tol, rank_tol; } osot_qp_sens_options;   /* 0 = 1e-8, 1e-9, 1e-11 */
+typedef struct osot_qp_sens_batch {
+    int B, n, nc;
+    const double *H, *g, *A, *lA, *uA, *l, *u;          /* as osot_qp_solve_batch (A, lA, uA: nc > 0; l, u: both or neither)         */
+    double eps_abs;
+    const double* x;                                    /* [B][n]                                                                    */
+    const int* status;                                  /* [B] OSOT_STATUS_* or NULL = all solved                                    */
+    const double* grad_x;                               /* [B][n] or NULL: multipliers only                                          */
+    double* y;                                          /* [B][n + nc] or NULL                                                       */
+    int* active;                                        /* [B][n + nc] or NULL                                                       */
+    double *grad_H, *grad_g, *grad_A, *grad_lA, *grad_uA, *grad_l, *grad_u;   /* shaped as the inputs; any may be NULL               */
+    int* flag;                                          /* [B] OSOT_SENS_*                                                           */
+} osot_qp_sens_batch;
+/* Stream-ordered, no allocation, no synchronisation, capturable; B == 0 is a no-op.  (33 .. 64 variables need more than 64 KB of
+ * LDS: the first such launch on a device raises the kernel's limit, a host-side setting made once; make that launch before a
+ * capture.)  options NULL, or a tolerance of 0: the default.  Refused before any device is touched (osot_last_error() says why):
+ * n > 64 with OSOT_ERR_UNSUPPORTED (65 .. 128 variables are not built); with OSOT_ERR_INVALID B < 0, n < 1, nc < 0, a negative
+ * tolerance or eps_abs, H / g / x / flag NULL, nc > 0 with A NULL, A without lA and uA, l without u, a gradient output without
+ * grad_x, an output that aliases an input. */
+int osot_qp_sensitivity_batch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream);
+
 /* ---- layout of the structs above as THIS library was compiled (for bindings that mirror them by hand: ctypes, cgo, JNI ...).
  * name = the typedef's name ("osot_plan_desc", "osot_qp_batch", ...).  *size = sizeof; the byte offset of every member, in
  * declaration order, goes to offsets[0 .. *n_fields) (at most max_fields are written; offsets may be NULL).  Unknown name:

@@ -291,6 +291,21 @@ class AccBatch(C.Structure):
                 ("Minv", C.c_void_p), ("Minv_stride", C.c_longlong), ("ok", C.c_void_p)]
 
 
+SENS_OK, SENS_DEGENERATE, SENS_SKIPPED = 0, 1, 2
+
+
+class QpSensOptions(C.Structure):
+    _fields_ = [("active_tol", C.c_double), ("dual_tol", C.c_double), ("rank_tol", C.c_double)]
+
+
+class QpSensBatch(C.Structure):
+    _fields_ = [("B", C.c_int), ("n", C.c_int), ("nc", C.c_int),
+                ("H", C.c_void_p), ("g", C.c_void_p), ("A", C.c_void_p), ("lA", C.c_void_p), ("uA", C.c_void_p), ("l", C.c_void_p), ("u", C.c_void_p),
+                ("eps_abs", C.c_double), ("x", C.c_void_p), ("status", C.c_void_p), ("grad_x", C.c_void_p), ("y", C.c_void_p), ("active", C.c_void_p),
+                ("grad_H", C.c_void_p), ("grad_g", C.c_void_p), ("grad_A", C.c_void_p), ("grad_lA", C.c_void_p), ("grad_uA", C.c_void_p),
+                ("grad_l", C.c_void_p), ("grad_u", C.c_void_p), ("flag", C.c_void_p)]
+
+
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
     "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
@@ -306,7 +321,7 @@ SYMBOLS = [
     "osot_backend_set_eps_regularisation", "osot_backend_get_eps_regularisation",
     "osot_backend_get_num_variables", "osot_backend_get_num_constraints",
     "osot_qp_solve_batch", "osot_qp_solve_batch_admm", "osot_qp_solve_batch_admm_warm",
-    "osot_qp_hot_state_ints", "osot_qp_solve_batch_hot",
+    "osot_qp_hot_state_ints", "osot_qp_solve_batch_hot", "osot_qp_sensitivity_batch",
     "osot_solver_hot_state_ints", "osot_ihqp_solve_hot", "osot_cycle_hot",
     "osot_comm_unique_id", "osot_comm_create", "osot_comm_destroy", "osot_allgather_dq", "osot_abi_layout",
 ]
@@ -319,7 +334,8 @@ STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound
            "osot_dyn_desc": DynDesc, "osot_dyn_batch": DynBatch, "osot_grad_desc": GradDesc, "osot_grad_batch": GradBatch, "osot_shape": Shape,
            "osot_force_model": ForceModel, "osot_force_batch": ForceBatch,
            "osot_feedback_model": FeedbackModel, "osot_feedback_batch": FeedbackBatch,
-           "osot_acc_model": AccModel, "osot_acc_batch": AccBatch}
+           "osot_acc_model": AccModel, "osot_acc_batch": AccBatch,
+           "osot_qp_sens_options": QpSensOptions, "osot_qp_sens_batch": QpSensBatch}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -418,6 +434,7 @@ def lib():
                                            C.c_double, C.c_int, vp, vp, vp, vp]
     L.osot_qp_solve_batch_admm_warm.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                                 C.c_double, C.POINTER(AdmmOptions), vp, vp, vp, vp, vp, vp, vp]
+    L.osot_qp_sensitivity_batch.argtypes = [C.POINTER(QpSensBatch), C.POINTER(QpSensOptions), vp]
     L.osot_comm_unique_id.argtypes = [vp]
     L.osot_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.osot_comm_destroy.argtypes = [vp]

@@ -25,6 +25,7 @@
 #include "osot_force.h"
 #include "osot_feedback.h"
 #include "osot_acc.h"
+#include "osot_qp_sens.h"
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
 #include "osot_qp_big.h"
@@ -245,6 +246,10 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
         OSOT_F(cart_p0) OSOT_F(cart_p0_stride) OSOT_F(cart_a_ref_out) OSOT_F(cart_Mi) OSOT_F(com_J) OSOT_F(com_J_stride) OSOT_F(com_J_ld)
         OSOT_F(com) OSOT_F(com_ref) OSOT_F(com_vel_ref) OSOT_F(com_p0) OSOT_F(com_p0_stride) OSOT_F(post_q_ref) OSOT_F(post_qdot_ref)
         OSOT_F(post_qddot_ref) OSOT_F(post_p0) OSOT_F(post_qddot_out) OSOT_F(Minv) OSOT_F(Minv_stride) OSOT_F(ok) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_qp_sens_options) OSOT_F(active_tol) OSOT_F(dual_tol) OSOT_F(rank_tol) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_qp_sens_batch) OSOT_F(B) OSOT_F(n) OSOT_F(nc) OSOT_F(H) OSOT_F(g) OSOT_F(A) OSOT_F(lA) OSOT_F(uA) OSOT_F(l) OSOT_F(u)
+        OSOT_F(eps_abs) OSOT_F(x) OSOT_F(status) OSOT_F(grad_x) OSOT_F(y) OSOT_F(active) OSOT_F(grad_H) OSOT_F(grad_g) OSOT_F(grad_A)
+        OSOT_F(grad_lA) OSOT_F(grad_uA) OSOT_F(grad_l) OSOT_F(grad_u) OSOT_F(flag) OSOT_LAYOUT_END()
 #undef OSOT_LAYOUT_BEGIN
 #undef OSOT_F
 #undef OSOT_LAYOUT_END
@@ -1604,6 +1609,33 @@ int osot_acc_tasks(const osot_acc_model* m, const osot_acc_batch* b, void* hip_s
     AccArgs A;
     A.M = *m; A.Bt = *b;
     hipLaunchKernelGGL(osot_acc_tasks_kernel, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, A);
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// multipliers, active set and backward pass of the explicit QP (osot_qp_sens.h): one wavefront per instance, n <= 64
+int osot_qp_sensitivity_batch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream) {
+    const char* why = "";
+    int rc = sens_check(b, opt, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_qp_sensitivity_batch: ") + why);
+    if (b->B == 0) return OSOT_OK;
+    const size_t lds = (size_t)sens_lds_bytes(b->n);   // 29.9 KB at n = 32, 107.8 KB at n = 64
+    if (lds > 64 * 1024) {
+        // the limit is raised to the largest slice there is, ONCE per device: later launches, captured ones included, only launch
+        static unsigned long long raised = 0ull;     // bit d: done on device d (benign if two threads both do it)
+        int device = 0;
+        HIP_TRY(hipGetDevice(&device));
+        if (device < 0 || device >= 64 || !((raised >> device) & 1ull)) {
+            rc = ensure_lds(osot_qp_sens_kernel<64>, (size_t)sens_lds_bytes(OSOT_MAX_VARS));
+            if (rc != OSOT_OK) return rc;
+            if (device >= 0 && device < 64) raised |= 1ull << device;
+        }
+    }
+    SensArgs S;
+    S.b = *b;
+    sens_options(opt, &S.active_tol, &S.dual_tol, &S.rank_tol);
+    if (b->n <= 32) hipLaunchKernelGGL(osot_qp_sens_kernel<32>, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, S);
+    else hipLaunchKernelGGL(osot_qp_sens_kernel<64>, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, S);
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

@@ -5,6 +5,8 @@ at once on CUDA/HIP tensors: the device pointers of the caller's tensors go STRA
 results come back as tensors on the same device and stream -- no host copies, no staging.
 
     qp_solve(H, g, A, lA, uA, l, u, ...)   B generic QPs in BackEnd convention through either back-end
+    qp_multipliers(..., x)                 their multipliers and active sets (QPOasesBackEnd::getDualSolution / getActiveBounds)
+    qp_layer(H, g, A, lA, uA, l, u)        the active-set solve as a differentiable layer (n <= 64)
     iHQP / nHQP                            the cascade front-ends on a BatchedStack, `solve()` returning dq as a tensor
 """
 import ctypes as C
@@ -111,6 +113,114 @@ def qp_solve(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=
                                               C.c_void_p(x.data_ptr()), C.c_void_p(status.data_ptr()),
                                               C.c_void_p(iters.data_ptr()), stream), "osot_qp_solve_batch")
     return x, status, iters
+
+
+def _sens_batch(H, g, A, lA, uA, l, u, x, status, eps_regularisation):
+    """abi.QpSensBatch with the inputs bound (outputs are the caller's to bind) -> (batch, B, n, nc)"""
+    if H.dim() != 3 or H.shape[1] != H.shape[2]:
+        raise ValueError("H must be [B][n][n]")
+    B, n = H.shape[0], H.shape[1]
+    nc = 0 if A is None else A.shape[1]
+    b = abi.QpSensBatch()
+    b.B, b.n, b.nc, b.eps_abs = B, n, nc, eps_abs_from_factor(eps_regularisation)
+    b.H, b.g = _chk(H, "H"), _chk(g, "g", (B, n))
+    if nc:
+        b.A, b.lA, b.uA = _chk(A, "A", (B, nc, n)), _chk(lA, "lA", (B, nc)), _chk(uA, "uA", (B, nc))
+    b.l, b.u = _chk(l, "l", (B, n)), _chk(u, "u", (B, n))
+    b.x = _chk(x, "x", (B, n))
+    b.status = _chk(status, "status", (B,), dtype=torch.int32)
+    return b, B, n, nc
+
+
+def _ptr(t):
+    return C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None
+
+
+def _sens_options(options):
+    if options is None:
+        return None
+    o = abi.QpSensOptions()
+    o.active_tol, o.dual_tol, o.rank_tol = (float(options.get(k, 0.0)) for k in ("active_tol", "dual_tol", "rank_tol"))
+    return C.byref(o)
+
+
+def qp_multipliers(H, g, A, lA, uA, l, u, x, status=None, eps_regularisation=2e2, options=None):
+    """The multipliers and the active set of B QPs at their solutions x [B][n] (qp_solve's, or anybody's): what QPOasesBackEnd keeps as
+    getDualSolution (nV + nC entries, the bounds first; QPOasesBackEnd.cpp:153-158) and getActiveBounds / getActiveConstraints.
+    status [B] int32 (qp_solve's) or None = all solved.  options: dict with active_tol, dual_tol, rank_tol (0 or absent = 1e-8, 1e-9,
+    1e-11).  n <= 64; 65 .. 128 variables are not built (RuntimeError).
+    Returns (y [B][n + nc] float64 in qpOASES' convention: H~ x + g = y_b + A' y_c, y > 0 on a lower side, y < 0 on an upper side;
+    active [B][n + nc] int32: 0, -1 lower, +1 upper, 2 equality; flag [B] int32 OSOT_SENS_*: 0 unique, 1 degenerate (a valid one-sided
+    answer), 2 skipped (not solved, x not finite or H + eps I not positive definite: zeros)), stream-ordered on the current stream."""
+    b, B, n, nc = _sens_batch(H, g, A, lA, uA, l, u, x, status, eps_regularisation)
+    dev = H.device
+    y = torch.empty((B, n + nc), dtype=torch.float64, device=dev)
+    active = torch.empty((B, n + nc), dtype=torch.int32, device=dev)
+    flag = torch.empty((B,), dtype=torch.int32, device=dev)
+    b.y, b.active, b.flag = _ptr(y), _ptr(active), _ptr(flag)
+    with torch.cuda.device(dev):
+        abi.check(abi.lib().osot_qp_sensitivity_batch(C.byref(b), _sens_options(options), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
+                  "osot_qp_sensitivity_batch")
+    return y, active, flag
+
+
+class _QpLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, H, g, A, lA, uA, l, u, eps_regularisation, max_iter, hot, last):
+        x, status, iters = qp_solve(H, g, A, lA, uA, l, u, eps_regularisation=eps_regularisation, max_iter=max_iter, hot=hot)
+        last.status, last.iterations = status, iters
+        last.flag = torch.full((H.shape[0],), -1, dtype=torch.int32, device=H.device)      # filled by the backward pass
+        ctx.save_for_backward(*[t for t in (H, g, A, lA, uA, l, u, x, status) if t is not None])
+        ctx.present = [t is not None for t in (H, g, A, lA, uA, l, u)]
+        ctx.eps, ctx.last = eps_regularisation, last
+        return x
+
+    @staticmethod
+    def backward(ctx, grad_x):
+        saved = list(ctx.saved_tensors)
+        H, g, A, lA, uA, l, u = (saved.pop(0) if p else None for p in ctx.present)
+        x, status = saved
+        b, B, n, nc = _sens_batch(H, g, A, lA, uA, l, u, x, status, ctx.eps)
+        gx = grad_x.contiguous()
+        b.grad_x, b.flag = _ptr(gx), _ptr(ctx.last.flag)
+        grads = []
+        for k, (name, t) in enumerate(zip(("grad_H", "grad_g", "grad_A", "grad_lA", "grad_uA", "grad_l", "grad_u"), (H, g, A, lA, uA, l, u))):
+            out = None
+            if t is not None and ctx.needs_input_grad[k]:      # NULL for every input that does not need a gradient
+                out = torch.empty_like(t)
+                setattr(b, name, _ptr(out))
+            grads.append(out)
+        ctx.last.bound = [name for name, o in zip(("H", "g", "A", "lA", "uA", "l", "u"), grads) if o is not None]
+        with torch.cuda.device(H.device):
+            abi.check(abi.lib().osot_qp_sensitivity_batch(C.byref(b), None, C.c_void_p(torch.cuda.current_stream(H.device).cuda_stream)),
+                      "osot_qp_sensitivity_batch")
+        return (*grads, None, None, None, None)
+
+
+class _QpLayerLast:
+    """what the last qp_layer call left: status, iterations [B] int32 of the solve; flag [B] int32 OSOT_SENS_* of the backward pass (-1 until
+    it has run); bound: the inputs whose gradient outputs the backward pass handed to the kernel"""
+    status = iterations = flag = None
+    bound = ()
+
+
+def qp_layer(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=2e2, max_iter=0, hot=None):
+    """qp_solve through the active-set back-end as a differentiable layer: x [B][n] carries autograd's graph to H, g, A, lA, uA, l, u
+    (those that require a gradient).  The backward pass is one launch of osot_qp_sensitivity_batch: the active set at x, its
+    multipliers and one more solve of the same KKT system with the upstream gradient on the right-hand side; grad_H is symmetric
+    (the derivative with respect to a symmetric H), an equality's gradient goes to its lower bound.  An instance that was not solved
+    (status != 0) or that the backward pass skipped contributes a zero gradient; at a degenerate solution (flag 1) the gradient is a
+    valid one-sided one.  `qp_layer.last` holds status, iterations and flag of the most recent call.
+    n <= 64 (ValueError above; the solve alone goes to 128 through qp_solve).  The OSQP-convention back-end is not offered as a layer:
+    its solutions stop at 1e-5, too far from a vertex to read the active set from."""
+    if H.dim() == 3 and H.shape[1] > 64:
+        raise ValueError("qp_layer: more than 64 variables (the backward pass is built for n <= 64; qp_solve alone takes up to 128)")
+    last = _QpLayerLast()
+    qp_layer.last = last
+    return _QpLayer.apply(H, g, A, lA, uA, l, u, eps_regularisation, max_iter, hot, last)
+
+
+qp_layer.last = _QpLayerLast()
 
 
 class iHQP:
