@@ -1347,6 +1347,85 @@ typedef struct osot_qp_sens_batch {
  * grad_x, an output that aliases an input. */
 int osot_qp_sensitivity_batch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream);
 
+/* ---- the QP of every level of the batched iHQP cascade, its multipliers, active set and objective (opensot_amd/csrc/osot_ihqp_sens.h)
+ * What iHQP exposes besides solve(): getBackEnd(i) (the level's H, g, A, lA, uA, l, u, iHQP.cpp:381-389, BackEnd.h), on the default
+ * back-end the dual solution and the working set of that level (QPOasesBackEnd.h:163-172), and getObjective(i).  For handles of
+ * osot_solver_create (the wavefront route, n <= 64); a handle of osot_solver_create_wide is refused with OSOT_ERR_UNSUPPORTED before
+ * any device is touched.
+ *
+ * THE LEVEL QP, for the inputs of an osot_qp_batch and the x_levels its solve left behind:
+ *   H [B][n][n] ........ A_k' W_k A_k, full and symmetric to the bit, WITHOUT eps_abs: the stored rows (w[k] on the diagonal, or the
+ *                        WA / Wb operands of a level with a non-diagonal weight), the rows of a regularisation task with a stored
+ *                        Jacobian, then on the diagonal the weights of the level's implicit Postural block and of an
+ *                        identity-Jacobian regularisation task.  The rows of an inactive task count with weight zero.
+ *   g [B][n] ........... -A_k' W_k b_k (+ the regularisation task's) + c[k]
+ *   A [B][rows][n], lA, uA [B][rows] with rows = nc + (task rows of the levels 0 .. level-1), osot_ihqp_level_rows:
+ *     rows 0 .. nc-1 ... the plan's row blocks in plan order: stored rows from C, unit-row blocks as e_(first_col+i), lo / up clamped
+ *                        to +-1e20; a task-local block (only_level) is a zero row with -1e20 / 1e20 at every level but its own.
+ *     then, per level j < level in level order, its m_j task rows with lA = uA = a_r' x_j (x_j = x_levels[.][j]; one fma chain over
+ *                        the columns in ascending order): stored rows from A[j], the implicit Postural block as e_i with the
+ *                        bound x_j[i]; the rows of an inactive task are zero rows with -1e20 / 1e20; a level switched off by
+ *                        level_active gives zero rows with -1 / 1 (iHQP.cpp:301-309).
+ *   l, u [B][n] ........ the merged box clamped to +-1e20, or -1e20 / 1e20 where the plan has no bounds. */
+typedef struct osot_level_qp { double *H, *g, *A, *lA, *uA, *l, *u; } osot_level_qp;   /* device pointers, all required */
+/* rows of the QP of `level` (host only).  OSOT_ERR_INVALID: a null argument, level outside 0 .. n_levels-1. */
+int osot_ihqp_level_rows(osot_solver* s, int level, int* rows);
+/* One launch, stream-ordered, no allocation, capturable.  batch: as for osot_ihqp_solve, with x_levels (its level_active and the
+ * handle's osot_solver_set_task_active flags are the ones of the solve).  OSOT_ERR_INVALID: a null argument or member of out, level
+ * out of range, B outside 0 .. max_batch, what osot_ihqp_solve refuses of a batch, x_levels NULL for level > 0. */
+int osot_ihqp_level_qp(osot_solver* s, const osot_qp_batch* batch, int level, const osot_level_qp* out, void* hip_stream);
+
+/* Multipliers, active set, flag and objective of EVERY level, after a solve.  Per active level, from the last one down, three
+ * launches on the stream: the level QP into the workspace, osot_qp_sensitivity_batch's kernel on it with x = x_levels[.][k]
+ * (conventions, tolerances and flags: above), and the objective.
+ *   qp ............ the batch of the solve just made; x_levels and status are required
+ *   y[k] .......... [B][n + rows_k] qpOASES' sign, the n bounds first (rows_k: osot_ihqp_level_rows); active[k] likewise; flag[k] [B].
+ *                   One pointer per level, each may be NULL.
+ *   objective ..... [B][n_levels] or NULL: 1/2 x_k'(H_k + eps_abs I) x_k + g_k' x_k, qpOASES' getObjVal() of the level
+ *   workspace ..... device memory of the caller, at least osot_ihqp_sens_workspace_bytes, 8-byte aligned
+ * An instance whose status is not OSOT_STATUS_SOLVED is OSOT_SENS_SKIPPED at every level (zeros); so is every instance at a level
+ * that level_active switches off.  Nothing non-finite is written.
+ * Stream-ordered, no allocation, no synchronisation, capturable (33 .. 64 variables: after one eager call on the device, see
+ * osot_qp_sensitivity_batch).  Refused before any device is touched (osot_last_error() says why): a wide handle
+ * (OSOT_ERR_UNSUPPORTED); with OSOT_ERR_INVALID a null argument, B outside 0 .. max_batch, what osot_ihqp_solve refuses of qp,
+ * x_levels or status NULL, workspace NULL or smaller than needed, a bad tolerance, an output that overlaps an input, the workspace
+ * or another output (the workspace by its byte range; the others by their first address).  "Nothing non-finite is written" holds
+ * for the outputs: the workspace of an instance that was not solved holds whatever x_levels held.
+ *
+ * BACKWARD (grad_dq given): the gradients of a loss with respect to the assembled inputs of the cascade, given grad_dq = d loss / d dq.
+ * The levels run from the last active one down; level k's multiplier launch also solves its KKT system for gx_k (gx of the last
+ * active level is grad_dq) and a pull-back launch per level hands the result on: with dx the level's grad_g, s_r = a_r'x_k and
+ * t_r = a_r'dx on the task rows of level k,
+ *   grad_b[k][r] = -w_r t_r, grad_w[k][r] = t_r (s_r - b_r), grad_c[k] = dx, grad_A[k][r] += w_r ((s_r - b_r) dx + t_r x_k);
+ *   summed over the levels: grad_lo / grad_up += the QP's grad_lA / grad_uA on the global rows, grad_C += its grad_A on the stored
+ *   global rows, grad_l / grad_u += its grad_l / grad_u; on the optimality block of level j < k, with rho = grad_lA + grad_uA:
+ *   gx_j += A_j' rho, grad_A[j][r] += grad_A_qp[row] + rho_r x_j'.  (Implicit Postural rows have no storage: gx_j and grad_b / grad_w only.)
+ * Every gradient output may be NULL; all are zeroed by the call first (stream-ordered fills), then accumulated.  grad_b[k], grad_w[k]
+ * [B][m_k], grad_c[k] [B][n], grad_A[k] [B][ma_k][n], grad_C [B][nc_stored][n], grad_lo / grad_up [B][nc], grad_l / grad_u [B][n].
+ * A DEGENERATE level gives the one-sided answer of osot_qp_sensitivity_batch (flag[k] says so); a SKIPPED instance zero gradients.
+ * Refused: a gradient output without grad_dq (OSOT_ERR_INVALID); grad_dq on a plan with a dense-weight level or a regularisation
+ * task (OSOT_ERR_UNSUPPORTED: forward works for them). */
+typedef struct osot_ihqp_sens_batch {
+    osot_qp_batch qp;
+    double* y[OSOT_MAX_LEVELS];
+    int* active[OSOT_MAX_LEVELS];
+    int* flag[OSOT_MAX_LEVELS];
+    double* objective;
+    void* workspace;
+    unsigned long long workspace_bytes;
+    const double* grad_dq;                              /* [B][n] or NULL: forward only */
+    double* grad_b[OSOT_MAX_LEVELS];
+    double* grad_w[OSOT_MAX_LEVELS];
+    double* grad_c[OSOT_MAX_LEVELS];
+    double* grad_A[OSOT_MAX_LEVELS];
+    double *grad_C, *grad_lo, *grad_up, *grad_l, *grad_u;
+} osot_ihqp_sens_batch;
+/* bytes of workspace for B instances (host only), rows = the last level's.  Forward: 8 (B (n n + rows n + 2 rows + 4 n) + (B + 1) / 2):
+ * one level QP, x of the level and a flag per instance.  want_backward adds 8 B (3 n + 2 rows + L n) (dx, the QP's bound gradients,
+ * gx of every level), want_grad_A (grad_A[k] or grad_C will be asked for) 8 B rows n more (the QP's grad_A). */
+int osot_ihqp_sens_workspace_bytes(osot_solver* s, int B, int want_backward, int want_grad_A, unsigned long long* bytes);
+int osot_ihqp_sensitivity(osot_solver* s, const osot_ihqp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream);
+
 /* ---- layout of the structs above as THIS library was compiled (for bindings that mirror them by hand: ctypes, cgo, JNI ...).
  * name = the typedef's name ("osot_plan_desc", "osot_qp_batch", ...).  *size = sizeof; the byte offset of every member, in
  * declaration order, goes to offsets[0 .. *n_fields) (at most max_fields are written; offsets may be NULL).  Unknown name:

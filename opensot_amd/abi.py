@@ -306,6 +306,18 @@ class QpSensBatch(C.Structure):
                 ("grad_l", C.c_void_p), ("grad_u", C.c_void_p), ("flag", C.c_void_p)]
 
 
+class LevelQp(C.Structure):
+    _fields_ = [("H", C.c_void_p), ("g", C.c_void_p), ("A", C.c_void_p), ("lA", C.c_void_p), ("uA", C.c_void_p), ("l", C.c_void_p), ("u", C.c_void_p)]
+
+
+class IhqpSensBatch(C.Structure):
+    _fields_ = [("qp", QpBatch), ("y", C.c_void_p * MAX_LEVELS), ("active", C.c_void_p * MAX_LEVELS), ("flag", C.c_void_p * MAX_LEVELS),
+                ("objective", C.c_void_p), ("workspace", C.c_void_p), ("workspace_bytes", C.c_ulonglong),
+                ("grad_dq", C.c_void_p), ("grad_b", C.c_void_p * MAX_LEVELS), ("grad_w", C.c_void_p * MAX_LEVELS),
+                ("grad_c", C.c_void_p * MAX_LEVELS), ("grad_A", C.c_void_p * MAX_LEVELS), ("grad_C", C.c_void_p), ("grad_lo", C.c_void_p),
+                ("grad_up", C.c_void_p), ("grad_l", C.c_void_p), ("grad_u", C.c_void_p)]
+
+
 SYMBOLS = [
     "osot_version", "osot_last_error", "osot_device_count",
     "osot_plan_validate", "osot_plan_validate_wide", "osot_solver_create_wide", "osot_plan_level_rows", "osot_plan_constraint_rows",
@@ -322,6 +334,7 @@ SYMBOLS = [
     "osot_backend_get_num_variables", "osot_backend_get_num_constraints",
     "osot_qp_solve_batch", "osot_qp_solve_batch_admm", "osot_qp_solve_batch_admm_warm",
     "osot_qp_hot_state_ints", "osot_qp_solve_batch_hot", "osot_qp_sensitivity_batch",
+    "osot_ihqp_level_rows", "osot_ihqp_level_qp", "osot_ihqp_sens_workspace_bytes", "osot_ihqp_sensitivity",
     "osot_solver_hot_state_ints", "osot_ihqp_solve_hot", "osot_cycle_hot",
     "osot_comm_unique_id", "osot_comm_create", "osot_comm_destroy", "osot_allgather_dq", "osot_abi_layout",
 ]
@@ -335,7 +348,8 @@ STRUCTS = {"osot_task_desc": TaskDesc, "osot_level_desc": LevelDesc, "osot_bound
            "osot_force_model": ForceModel, "osot_force_batch": ForceBatch,
            "osot_feedback_model": FeedbackModel, "osot_feedback_batch": FeedbackBatch,
            "osot_acc_model": AccModel, "osot_acc_batch": AccBatch,
-           "osot_qp_sens_options": QpSensOptions, "osot_qp_sens_batch": QpSensBatch}
+           "osot_qp_sens_options": QpSensOptions, "osot_qp_sens_batch": QpSensBatch,
+           "osot_level_qp": LevelQp, "osot_ihqp_sens_batch": IhqpSensBatch}
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # (OSOT_MI355X_LIB: developer override, to A/B two builds of the HIP library on the GPU box)
@@ -435,6 +449,10 @@ def lib():
     L.osot_qp_solve_batch_admm_warm.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                                 C.c_double, C.POINTER(AdmmOptions), vp, vp, vp, vp, vp, vp, vp]
     L.osot_qp_sensitivity_batch.argtypes = [C.POINTER(QpSensBatch), C.POINTER(QpSensOptions), vp]
+    L.osot_ihqp_level_rows.argtypes = [vp, C.c_int, ip]
+    L.osot_ihqp_level_qp.argtypes = [vp, C.POINTER(QpBatch), C.c_int, C.POINTER(LevelQp), vp]
+    L.osot_ihqp_sens_workspace_bytes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]
+    L.osot_ihqp_sensitivity.argtypes = [vp, C.POINTER(IhqpSensBatch), C.POINTER(QpSensOptions), vp]
     L.osot_comm_unique_id.argtypes = [vp]
     L.osot_comm_create.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(vp)]
     L.osot_comm_destroy.argtypes = [vp]

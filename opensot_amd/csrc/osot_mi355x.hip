@@ -26,6 +26,7 @@
 #include "osot_feedback.h"
 #include "osot_acc.h"
 #include "osot_qp_sens.h"
+#include "osot_ihqp_sens.h"
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
 #include "osot_qp_big.h"
@@ -250,6 +251,10 @@ int osot_abi_layout(const char* name, unsigned long long* size, unsigned long lo
     OSOT_LAYOUT_BEGIN(osot_qp_sens_batch) OSOT_F(B) OSOT_F(n) OSOT_F(nc) OSOT_F(H) OSOT_F(g) OSOT_F(A) OSOT_F(lA) OSOT_F(uA) OSOT_F(l) OSOT_F(u)
         OSOT_F(eps_abs) OSOT_F(x) OSOT_F(status) OSOT_F(grad_x) OSOT_F(y) OSOT_F(active) OSOT_F(grad_H) OSOT_F(grad_g) OSOT_F(grad_A)
         OSOT_F(grad_lA) OSOT_F(grad_uA) OSOT_F(grad_l) OSOT_F(grad_u) OSOT_F(flag) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_level_qp) OSOT_F(H) OSOT_F(g) OSOT_F(A) OSOT_F(lA) OSOT_F(uA) OSOT_F(l) OSOT_F(u) OSOT_LAYOUT_END()
+    OSOT_LAYOUT_BEGIN(osot_ihqp_sens_batch) OSOT_F(qp) OSOT_F(y) OSOT_F(active) OSOT_F(flag) OSOT_F(objective) OSOT_F(workspace)
+        OSOT_F(workspace_bytes) OSOT_F(grad_dq) OSOT_F(grad_b) OSOT_F(grad_w) OSOT_F(grad_c) OSOT_F(grad_A) OSOT_F(grad_C) OSOT_F(grad_lo)
+        OSOT_F(grad_up) OSOT_F(grad_l) OSOT_F(grad_u) OSOT_LAYOUT_END()
 #undef OSOT_LAYOUT_BEGIN
 #undef OSOT_F
 #undef OSOT_LAYOUT_END
@@ -1614,11 +1619,17 @@ int osot_acc_tasks(const osot_acc_model* m, const osot_acc_batch* b, void* hip_s
 }
 
 // multipliers, active set and backward pass of the explicit QP (osot_qp_sens.h): one wavefront per instance, n <= 64
+static int sens_launch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream);
 int osot_qp_sensitivity_batch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream) {
     const char* why = "";
     int rc = sens_check(b, opt, &why);
     if (rc != OSOT_OK) return fail(rc, std::string("osot_qp_sensitivity_batch: ") + why);
     if (b->B == 0) return OSOT_OK;
+    return sens_launch(b, opt, hip_stream);
+}
+// the launch of osot_qp_sens_kernel on a checked batch (osot_ihqp_sensitivity launches it once per level)
+static int sens_launch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream) {
+    int rc = OSOT_OK;
     const size_t lds = (size_t)sens_lds_bytes(b->n);   // 29.9 KB at n = 32, 107.8 KB at n = 64
     if (lds > 64 * 1024) {
         // the limit is raised to the largest slice there is, ONCE per device: later launches, captured ones included, only launch
@@ -1636,6 +1647,69 @@ int osot_qp_sensitivity_batch(const osot_qp_sens_batch* b, const osot_qp_sens_op
     sens_options(opt, &S.active_tol, &S.dual_tol, &S.rank_tol);
     if (b->n <= 32) hipLaunchKernelGGL(osot_qp_sens_kernel<32>, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, S);
     else hipLaunchKernelGGL(osot_qp_sens_kernel<64>, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, S);
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// ---- the level QPs of the cascade, their multipliers, active sets and objectives (osot_ihqp_sens.h) -------------------------------
+int osot_ihqp_level_rows(osot_solver* s, int level, int* rows) {
+    if (!s || !rows) return fail(OSOT_ERR_INVALID, "osot_ihqp_level_rows: null argument");
+    if (level < 0 || level >= s->plan.n_levels) return fail(OSOT_ERR_INVALID, "osot_ihqp_level_rows: level out of range");
+    LevelPlan P;
+    make_plan_shape(s->plan, nullptr, nullptr, P);
+    *rows = level_qp_rows(P, level);
+    return OSOT_OK;
+}
+
+static void level_qp_launch(const LevelQpArgs& Q, hipStream_t st) {
+    const size_t lds = (size_t)level_qp_lds_bytes(Q.P.n);     // at most 33 792 bytes: below the default limit
+    if (Q.P.n <= 32) hipLaunchKernelGGL(osot_ihqp_level_qp_kernel<32>, dim3((unsigned)Q.D.B), dim3(64), lds, st, Q);
+    else hipLaunchKernelGGL(osot_ihqp_level_qp_kernel<64>, dim3((unsigned)Q.D.B), dim3(64), lds, st, Q);
+}
+
+int osot_ihqp_level_qp(osot_solver* s, const osot_qp_batch* b, int level, const osot_level_qp* out, void* hip_stream) {
+    if (!s) return fail(OSOT_ERR_INVALID, "osot_ihqp_level_qp: null solver");
+    LevelQpArgs Q;
+    const char* why = "";
+    const int rc = level_qp_check(s->plan, s->wide, s->max_batch, s->any_inactive ? s->task_active : nullptr, b, level, out, Q, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_ihqp_level_qp: ") + why);
+    if (b->B == 0) return OSOT_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    level_qp_launch(Q, (hipStream_t)hip_stream);
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+int osot_ihqp_sens_workspace_bytes(osot_solver* s, int B, int want_backward, int want_grad_A, unsigned long long* bytes) {
+    if (!s || !bytes) return fail(OSOT_ERR_INVALID, "osot_ihqp_sens_workspace_bytes: null argument");
+    if (s->wide) return fail(OSOT_ERR_UNSUPPORTED, "osot_ihqp_sens_workspace_bytes: per-level multipliers are built for handles of osot_solver_create, not for the wide route");
+    if (B < 0 || B > s->max_batch) return fail(OSOT_ERR_INVALID, "osot_ihqp_sens_workspace_bytes: batch size exceeds max_batch");
+    LevelPlan P;
+    make_plan_shape(s->plan, nullptr, nullptr, P);
+    *bytes = (unsigned long long)ihqp_sens_workspace(P, B, want_backward != 0, want_grad_A != 0).total * sizeof(double);
+    return OSOT_OK;
+}
+
+int osot_ihqp_sensitivity(osot_solver* s, const osot_ihqp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream) {
+    if (!s) return fail(OSOT_ERR_INVALID, "osot_ihqp_sensitivity: null solver");
+    LevelQpArgs Q;
+    const char* why = "";
+    const int rc = ihqp_sens_check(s->plan, s->wide, s->max_batch, s->any_inactive ? s->task_active : nullptr, b, opt, Q, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_ihqp_sensitivity: ") + why);
+    if (b->qp.B == 0) return OSOT_OK;
+    DeviceGuard guard(s->device);
+    if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
+    struct {
+        hipStream_t st; const osot_qp_sens_options* opt;
+        void level_qp(const LevelQpArgs& q) { level_qp_launch(q, st); }
+        int sens(const osot_qp_sens_batch& S) { return sens_launch(&S, opt, st); }
+        void objective(const ObjectiveArgs& O) { hipLaunchKernelGGL(osot_ihqp_objective_kernel, dim3((unsigned)O.B), dim3(64), (size_t)O.n * sizeof(double), st, O); }
+        void pullback(const PullbackArgs& R) { hipLaunchKernelGGL(osot_ihqp_pullback_kernel, dim3((unsigned)R.D.B), dim3(64), (size_t)pullback_lds_bytes(R.P.n), st, R); }
+        void zero(void* p, size_t bytes) { if (bytes) (void)hipMemsetAsync(p, 0, bytes, st); }
+        void copy(void* dst, const void* src, size_t bytes) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st); }
+    } go{(hipStream_t)hip_stream, opt};
+    if (const int r = ihqp_sens_levels(Q, b, go)) return r;
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

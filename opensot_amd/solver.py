@@ -274,6 +274,110 @@ class BatchedStack:
             return
         abi.check(self._lib.osot_ihqp_solve(self._h, C.byref(qb), _stream_ptr(self.device, self.stream)), "osot_ihqp_solve")
 
+    # ---- iHQP::getBackEnd(i), getObjective(i), the back-end's dual solution and working set -------------------------------------
+    def level_rows(self, k):
+        """rows of the QP of level k: the plan's constraint rows and the task rows of the levels above (osot_ihqp_level_rows)"""
+        v = C.c_int(0)
+        abi.check(self._lib.osot_ihqp_level_rows(self._h, int(k), C.byref(v)), "osot_ihqp_level_rows")
+        return v.value
+
+    def level_qp(self, k, B):
+        """the QP that the cascade solved at level k for the B instances of the last solve() (iHQP::getBackEnd(k): H, g, A, lA, uA, l,
+        u of BackEnd.h), built on the device from the stack's buffers and x_levels: dict of tensors H [B][n][n] (without eps), g [B][n],
+        A [B][rows][n], lA, uA [B][rows], l, u [B][n]; stream-ordered.  The wavefront route only."""
+        n, rows = self.plan.n, self.level_rows(k)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        out = dict(H=torch.empty((B, n, n), **f64), g=torch.empty((B, n), **f64), A=torch.empty((B, rows, n), **f64),
+                   lA=torch.empty((B, rows), **f64), uA=torch.empty((B, rows), **f64), l=torch.empty((B, n), **f64), u=torch.empty((B, n), **f64))
+        lq = abi.LevelQp()
+        for name, t in out.items():
+            setattr(lq, name, t.data_ptr())      # (an empty tensor still has storage to point at: rows may be 0)
+        no_rows = torch.empty((1,), **f64)       # (held until the call is enqueued: the three members must not be NULL)
+        if rows == 0:
+            lq.A = lq.lA = lq.uA = no_rows.data_ptr()
+        qb = self._qp_batch(B)
+        abi.check(self._lib.osot_ihqp_level_qp(self._h, C.byref(qb), int(k), C.byref(lq), _stream_ptr(self.device, self.stream)),
+                  "osot_ihqp_level_qp")
+        return out
+
+    def sens_workspace(self, B, backward=False, grad_A=False):
+        """the workspace of multipliers() / backward() for B instances (float64, osot_ihqp_sens_workspace_bytes); kept and reused while
+        it is large enough"""
+        v = C.c_ulonglong(0)
+        abi.check(self._lib.osot_ihqp_sens_workspace_bytes(self._h, int(B), int(bool(backward)), int(bool(grad_A)), C.byref(v)),
+                  "osot_ihqp_sens_workspace_bytes")
+        ws = getattr(self, "_sens_ws", None)
+        if ws is None or ws.numel() * 8 < v.value:
+            ws = self._sens_ws = torch.empty((max(1, v.value // 8),), dtype=torch.float64, device=self.device)
+        return ws, v.value
+
+    def multipliers(self, B, options=None, out=None):
+        """after solve(B): per level the dual solution, the working set and the objective of that level's QP (on the reference's
+        default back-end getDualSolution, getActiveBounds / getActiveConstraints, getObjVal).  Returns dict(y, active, flag: lists
+        with one tensor per level, y[k] [B][n + level_rows(k)] in qpOASES' sign with the bounds first, active[k] likewise (0, -1
+        lower, +1 upper, 2 equality), flag[k] [B] OSOT_SENS_*; objective [B][L]).  out: such a dict to write into (a captured graph
+        replays into the same tensors); options: dict with active_tol, dual_tol, rank_tol.  Stream-ordered; the wavefront route only;
+        needs want_levels."""
+        n, L = self.plan.n, self.plan.L
+        if out is None:
+            f64 = dict(dtype=torch.float64, device=self.device)
+            i32 = dict(dtype=torch.int32, device=self.device)
+            rows = [self.level_rows(k) for k in range(L)]
+            out = dict(y=[torch.empty((B, n + r), **f64) for r in rows], active=[torch.empty((B, n + r), **i32) for r in rows],
+                       flag=[torch.empty((B,), **i32) for _ in rows], objective=torch.empty((B, L), **f64))
+        s = abi.IhqpSensBatch()
+        s.qp = self._qp_batch(B)
+        for k in range(L):
+            s.y[k], s.active[k], s.flag[k] = out["y"][k].data_ptr(), out["active"][k].data_ptr(), out["flag"][k].data_ptr()
+        s.objective = out["objective"].data_ptr()
+        ws, nbytes = self.sens_workspace(B)
+        s.workspace, s.workspace_bytes = ws.data_ptr(), nbytes
+        o = None
+        if options is not None:
+            o = abi.QpSensOptions()
+            o.active_tol, o.dual_tol, o.rank_tol = (float(options.get(key, 0.0)) for key in ("active_tol", "dual_tol", "rank_tol"))
+        abi.check(self._lib.osot_ihqp_sensitivity(self._h, C.byref(s), None if o is None else C.byref(o), _stream_ptr(self.device, self.stream)),
+                  "osot_ihqp_sensitivity")
+        return out
+
+    def backward(self, B, grad_dq, want_A=False, options=None):
+        """after solve(B): the gradients of a loss with respect to the stack's assembled inputs, given grad_dq [B][n] = d loss / d dq
+        (osot_ihqp_sensitivity with grad_dq: every level's KKT system solved once more, linked by a pull-back launch per level).
+        Returns a dict shaped as the stack's own buffers: b, w, c (lists, one tensor per level: [B][m_k], [B][m_k], [B][n]), lo, up
+        [B][nc], l, u [B][n] (None where the stack has no such buffer), with want_A also A (list, [B][ma_k][n] or None) and C
+        [B][nc_stored][n]; and flag (list, [B] OSOT_SENS_* per level: 1 = a valid one-sided gradient, 2 = skipped, zero gradient).
+        Refused (RuntimeError with the reason): a wide stack, a plan with a dense-weight level or a regularisation task."""
+        n, L = self.plan.n, self.plan.L
+        if not (isinstance(grad_dq, torch.Tensor) and grad_dq.is_cuda and grad_dq.device == self.device and grad_dq.dtype == torch.float64
+                and grad_dq.is_contiguous() and tuple(grad_dq.shape) == (B, n)):
+            raise ValueError(f"grad_dq must be a contiguous float64 tensor [{B}][{n}] on {self.device}")
+        f64 = dict(dtype=torch.float64, device=self.device)
+        like = lambda t: None if t is None else torch.empty((B,) + tuple(t.shape[1:]), **f64)
+        g = dict(b=[like(t) for t in self.b], w=[like(t) for t in self.w], c=[torch.empty((B, n), **f64) for _ in range(L)],
+                 lo=like(self.lo), up=like(self.up), l=like(self.l), u=like(self.u),
+                 flag=[torch.empty((B,), dtype=torch.int32, device=self.device) for _ in range(L)])
+        if want_A:
+            g["A"], g["C"] = [like(t) for t in self.A], like(self.C)
+        s = abi.IhqpSensBatch()
+        s.qp = self._qp_batch(B)
+        s.grad_dq = grad_dq.data_ptr()
+        for k in range(L):
+            s.flag[k], s.grad_b[k], s.grad_w[k], s.grad_c[k] = g["flag"][k].data_ptr(), g["b"][k].data_ptr(), g["w"][k].data_ptr(), g["c"][k].data_ptr()
+            if want_A and g["A"][k] is not None:
+                s.grad_A[k] = g["A"][k].data_ptr()
+        for name in ("lo", "up", "l", "u") + (("C",) if want_A else ()):
+            if g[name] is not None:
+                setattr(s, "grad_" + name, g[name].data_ptr())
+        ws, nbytes = self.sens_workspace(B, True, want_A)
+        s.workspace, s.workspace_bytes = ws.data_ptr(), nbytes
+        o = None
+        if options is not None:
+            o = abi.QpSensOptions()
+            o.active_tol, o.dual_tol, o.rank_tol = (float(options.get(key, 0.0)) for key in ("active_tol", "dual_tol", "rank_tol"))
+        abi.check(self._lib.osot_ihqp_sensitivity(self._h, C.byref(s), None if o is None else C.byref(o), _stream_ptr(self.device, self.stream)),
+                  "osot_ihqp_sensitivity")
+        return g
+
     def hot_state(self, B=None):
         """the caller-owned hot-start state of the wide route for B (default max_batch) instances: int32 (B, L * 128) on the device,
         every entry -1 (no working set recorded: the first solve is a cold start); row i belongs to instance i.  Writing -1 to a

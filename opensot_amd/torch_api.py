@@ -7,7 +7,9 @@ results come back as tensors on the same device and stream -- no host copies, no
     qp_solve(H, g, A, lA, uA, l, u, ...)   B generic QPs in BackEnd convention through either back-end
     qp_multipliers(..., x)                 their multipliers and active sets (QPOasesBackEnd::getDualSolution / getActiveBounds)
     qp_layer(H, g, A, lA, uA, l, u)        the active-set solve as a differentiable layer (n <= 64)
-    iHQP / nHQP                            the cascade front-ends on a BatchedStack, `solve()` returning dq as a tensor
+    ihqp_layer(stack, b, w, lo, up, ...)   the cascade of a BatchedStack as a differentiable layer over its assembled inputs (n <= 64)
+    iHQP / nHQP                            the cascade front-ends on a BatchedStack, `solve()` returning dq as a tensor;
+                                           iHQP.getObjective(i) / getDualSolution(i) / getActiveSet(i) / getSensitivityFlag(i) / getLevelQP(i) after a solve
 """
 import ctypes as C
 import enum
@@ -223,6 +225,74 @@ def qp_layer(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=
 qp_layer.last = _QpLayerLast()
 
 
+class _IhqpLayer(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, stack, last, where, *tensors):
+        B = tensors[0].shape[0]
+        for (name, k), t in zip(where, tensors):
+            dst = getattr(stack, name)
+            (dst if k is None else dst[k])[:B].copy_(t)
+        stack.solve(B)
+        last.status = stack.status[:B].clone()
+        last.flag = None                                   # filled by the backward pass
+        ctx.stack, ctx.last, ctx.where, ctx.B = stack, last, where, B
+        return stack.dq[:B].clone()
+
+    @staticmethod
+    def backward(ctx, grad_dq):
+        need = ctx.needs_input_grad[3:]
+        want_A = any(n and name in ("A", "C") for n, (name, _) in zip(need, ctx.where))
+        g = ctx.stack.backward(ctx.B, grad_dq.contiguous(), want_A=want_A)
+        ctx.last.flag = g["flag"]
+        grads = [((g[name] if k is None else g[name][k]) if n else None) for n, (name, k) in zip(need, ctx.where)]
+        return (None, None, None, *grads)
+
+
+class _IhqpLayerLast:
+    """what the last ihqp_layer call left: status [B] int32 of the solve; flag: list of [B] int32 OSOT_SENS_* per level of the
+    backward pass (None until it has run)"""
+    status = flag = None
+
+
+def ihqp_layer(stack, b, w=None, lo=None, up=None, l=None, u=None, A=None, C=None):
+    """The cascade of a wavefront-route BatchedStack as a differentiable layer over its ASSEMBLED inputs: b, w, A are lists with one
+    tensor per level ([B][m_k], [B][m_k], [B][ma_k][n]; an entry, or the whole argument, may be None: the stack's buffer is used as it
+    is), lo, up [B][nc], l, u [B][n], C [B][nc_stored][n].  The tensors are copied into the stack's buffers, the stack is solved, and dq
+    [B][n] comes back carrying autograd's graph to those of them that require a gradient.  The backward pass is
+    BatchedStack.backward on the stack's buffers and x_levels AS THEY ARE THEN: run it before the stack is solved again.  An instance
+    that was not solved contributes a zero gradient; at a degenerate level the gradient is a valid one-sided one.  `ihqp_layer.last`
+    holds status and the levels' flags of the most recent call.  Raises before solving on a wide stack and on a plan with a
+    dense-weight level or a regularisation task (the backward pass is not built for them)."""
+    plan = stack.plan
+    if stack.route != "wavefront":
+        raise ValueError("ihqp_layer: the backward pass is built for the wavefront route (n <= 64), not for a wide stack")
+    if plan.regularisation is not None or any(plan.dense_level(k) for k in range(plan.L)):
+        raise ValueError("ihqp_layer: the backward pass is not built for plans with a dense-weight level or a regularisation task")
+    where, tensors = [], []
+    for name, v in (("b", b), ("w", w), ("A", A)):
+        for k, t in enumerate(v or []):
+            if t is not None:
+                where.append((name, k)); tensors.append(t)
+    for name, t in (("lo", lo), ("up", up), ("l", l), ("u", u), ("C", C)):
+        if t is not None:
+            where.append((name, None)); tensors.append(t)
+    if not tensors:
+        raise ValueError("ihqp_layer: no input tensor")
+    B = tensors[0].shape[0]
+    for (name, k), t in zip(where, tensors):
+        dst = getattr(stack, name)
+        dst = dst if k is None else dst[k]
+        if dst is None:
+            raise ValueError(f"ihqp_layer: the stack has no buffer {name}" + ("" if k is None else f"[{k}]"))
+        _chk(t, name, (B,) + tuple(dst.shape[1:]))
+    last = _IhqpLayerLast()
+    ihqp_layer.last = last
+    return _IhqpLayer.apply(stack, last, tuple(where), *tensors)
+
+
+ihqp_layer.last = _IhqpLayerLast()
+
+
 class iHQP:
     """pyopensot.iHQP for B instances of one stack (bindings/python/solver.hpp:67-91).  The stack's per-cycle inputs are the
     BatchedStack's device tensors (`self.stack.A[k]`, leaf dictionaries of tensors: the caller's producers write into them);
@@ -245,10 +315,44 @@ class iHQP:
         else:
             B = self.stack.max_batch if B is None else B
             self.stack.solve(B)
+        self._solved, self._sens = B, None
         return self.stack.dq[:B]
 
     def status(self, B=None):
         return self.stack.status[:(self.stack.max_batch if B is None else B)]
+
+    def _level_results(self, i):
+        """multipliers, working sets and objectives of every level of the last solve(): computed on the first question after it"""
+        if getattr(self, "_solved", None) is None:
+            raise RuntimeError("no solve() yet")
+        if not 0 <= i < self.stack.plan.L:
+            raise IndexError(f"level {i} of {self.stack.plan.L}")
+        if self._sens is None:
+            self._sens = self.stack.multipliers(self._solved)
+        return self._sens
+
+    def getObjective(self, i):
+        """iHQP::getObjective(i, val) (iHQP.cpp:381-389) of the last solve(): [B] tensor, the back-end's getObjVal() of level i"""
+        return self._level_results(i)["objective"][:, i]
+
+    def getDualSolution(self, i):
+        """the dual solution of level i's back-end (QPOasesBackEnd::getDualSolution): y [B][n + rows_i], qpOASES' sign, the bounds first"""
+        return self._level_results(i)["y"][i]
+
+    def getSensitivityFlag(self, i):
+        """[B] int32 OSOT_SENS_* of level i: 0 = the multipliers are unique, 1 = degenerate (a valid answer), 2 = skipped (zeros).  No
+        counterpart in the reference, whose back-end reports whatever its working set holds"""
+        return self._level_results(i)["flag"][i]
+
+    def getActiveSet(self, i):
+        """the working set of level i's back-end (getActiveBounds / getActiveConstraints): [B][n + rows_i] int32, the bounds first"""
+        return self._level_results(i)["active"][i]
+
+    def getLevelQP(self, i):
+        """iHQP::getBackEnd(i)'s problem data: dict H (without eps), g, A, lA, uA, l, u of the last solve()"""
+        if getattr(self, "_solved", None) is None:
+            raise RuntimeError("no solve() yet")
+        return self.stack.level_qp(i, self._solved)
 
     def getNumberOfTasks(self):
         return self.stack.plan.L
