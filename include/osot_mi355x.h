@@ -32,6 +32,8 @@
 #ifndef OSOT_MI355X_H
 #define OSOT_MI355X_H
 
+#include <stddef.h>   /* size_t */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -1346,6 +1348,25 @@ typedef struct osot_qp_sens_batch {
  * tolerance or eps_abs, H / g / x / flag NULL, nc > 0 with A NULL, A without lA and uA, l without u, a gradient output without
  * grad_x, an output that aliases an input. */
 int osot_qp_sensitivity_batch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream);
+
+/* The same call with a workspace of the caller's, for problems of up to OSOT_MAX_QP_VARS (128) variables
+ * (opensot_amd/csrc/osot_qp_sens_big.h).  n <= 64 is exactly osot_qp_sensitivity_batch: the same kernel, the same bits, and the
+ * workspace is not looked at (it may be NULL).  65 <= n <= 128 with nc <= 2048 runs one 256-thread workgroup per instance under
+ * the contract above, word for word; min(B, slots) workgroups walk the batch, each on its own slice of the workspace, so the
+ * workspace is sized by the slot count and not by B (n (2n + 2) doubles per slice).
+ *   osot_qp_sens_workspace_bytes ... host only, no GPU needed: the bytes the call needs for (B, n, nc); 0 for n <= 64 or B == 0.
+ *                                    OSOT_ERR_INVALID: bytes NULL, B < 0, n < 1, nc < 0; OSOT_ERR_UNSUPPORTED: n > 128, nc > 2048
+ *                                    with n > 64.
+ *   workspace ...................... device memory of the caller, 16-byte aligned, at least that many bytes; its content before
+ *                                    the call does not matter and is undefined after it.  One workspace serves one call at a time.
+ * Stream-ordered, no allocation, no synchronisation; B == 0 is a no-op.  The first launch on a device raises the kernel's LDS limit,
+ * a host-side setting made once: make one eager call before a capture.  Refused before any device is touched (osot_last_error()
+ * says why): everything osot_qp_sensitivity_batch refuses except 65 <= n <= 128; n > 128 and, with n > 64, nc > 2048
+ * (OSOT_ERR_UNSUPPORTED); with n > 64 and B > 0 a workspace that is NULL, not 16-byte aligned or smaller than
+ * osot_qp_sens_workspace_bytes, and an input or output whose first address lies inside the workspace (OSOT_ERR_INVALID). */
+int osot_qp_sens_workspace_bytes(int B, int n, int nc, size_t* bytes);
+int osot_qp_sensitivity_batch_ws(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* workspace, size_t workspace_bytes,
+                                 void* hip_stream);
 
 /* ---- the QP of every level of the batched iHQP cascade, its multipliers, active set and objective (opensot_amd/csrc/osot_ihqp_sens.h)
  * What iHQP exposes besides solve(): getBackEnd(i) (the level's H, g, A, lA, uA, l, u, iHQP.cpp:381-389, BackEnd.h), on the default

@@ -334,6 +334,7 @@ SYMBOLS = [
     "osot_backend_get_num_variables", "osot_backend_get_num_constraints",
     "osot_qp_solve_batch", "osot_qp_solve_batch_admm", "osot_qp_solve_batch_admm_warm",
     "osot_qp_hot_state_ints", "osot_qp_solve_batch_hot", "osot_qp_sensitivity_batch",
+    "osot_qp_sens_workspace_bytes", "osot_qp_sensitivity_batch_ws",
     "osot_ihqp_level_rows", "osot_ihqp_level_qp", "osot_ihqp_sens_workspace_bytes", "osot_ihqp_sensitivity",
     "osot_solver_hot_state_ints", "osot_ihqp_solve_hot", "osot_cycle_hot",
     "osot_comm_unique_id", "osot_comm_create", "osot_comm_destroy", "osot_allgather_dq", "osot_abi_layout",
@@ -449,6 +450,8 @@ def lib():
     L.osot_qp_solve_batch_admm_warm.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp, vp, vp,
                                                 C.c_double, C.POINTER(AdmmOptions), vp, vp, vp, vp, vp, vp, vp]
     L.osot_qp_sensitivity_batch.argtypes = [C.POINTER(QpSensBatch), C.POINTER(QpSensOptions), vp]
+    L.osot_qp_sens_workspace_bytes.argtypes = [C.c_int, C.c_int, C.c_int, C.POINTER(C.c_size_t)]
+    L.osot_qp_sensitivity_batch_ws.argtypes = [C.POINTER(QpSensBatch), C.POINTER(QpSensOptions), vp, C.c_size_t, vp]
     L.osot_ihqp_level_rows.argtypes = [vp, C.c_int, ip]
     L.osot_ihqp_level_qp.argtypes = [vp, C.POINTER(QpBatch), C.c_int, C.POINTER(LevelQp), vp]
     L.osot_ihqp_sens_workspace_bytes.argtypes = [vp, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_ulonglong)]

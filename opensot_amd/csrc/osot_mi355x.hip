@@ -26,6 +26,7 @@
 #include "osot_feedback.h"
 #include "osot_acc.h"
 #include "osot_qp_sens.h"
+#include "osot_qp_sens_big.h"
 #include "osot_ihqp_sens.h"
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
@@ -1647,6 +1648,46 @@ static int sens_launch(const osot_qp_sens_batch* b, const osot_qp_sens_options* 
     sens_options(opt, &S.active_tol, &S.dual_tol, &S.rank_tol);
     if (b->n <= 32) hipLaunchKernelGGL(osot_qp_sens_kernel<32>, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, S);
     else hipLaunchKernelGGL(osot_qp_sens_kernel<64>, dim3((unsigned)b->B), dim3(64), lds, (hipStream_t)hip_stream, S);
+    HIP_TRY(hipGetLastError());
+    return OSOT_OK;
+}
+
+// the same call with the caller's workspace: n <= 64 is the launch above, 65 .. 128 variables run one 256-thread workgroup per
+// instance (osot_qp_sens_big.h), min(B, slots) of them walking the batch, each on its own slice of the workspace
+int osot_qp_sens_workspace_bytes(int B, int n, int nc, size_t* bytes) {
+    const char* why = "";
+    const int rc = sens_ws_bytes_check(B, n, nc, bytes, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_qp_sens_workspace_bytes: ") + why);
+    *bytes = sensbig::workspace_bytes(B, n, nc);
+    return OSOT_OK;
+}
+int osot_qp_sensitivity_batch_ws(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* workspace, size_t workspace_bytes,
+                                 void* hip_stream) {
+    const char* why = "";
+    int rc = sens_ws_check(b, opt, workspace, workspace_bytes, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_qp_sensitivity_batch_ws: ") + why);
+    if (b->B == 0) return OSOT_OK;
+    if (b->n <= OSOT_MAX_VARS) return sens_launch(b, opt, hip_stream);
+    // 41.3 KiB of LDS at (65, 40) lets three workgroups share a CU, 145.1 KiB at (128, 24) one (derived: sensbig::lds_bytes).  The limit is
+    // raised to the largest there is, ONCE per device: later launches, captured ones included, only launch
+    const size_t lds = sensbig::lds_bytes(b->n, b->nc);
+    if (lds > 64 * 1024) {
+        static unsigned long long raised = 0ull;     // bit d: done on device d (benign if two threads both do it)
+        int device = 0;
+        HIP_TRY(hipGetDevice(&device));
+        if (device < 0 || device >= 64 || !((raised >> device) & 1ull)) {
+            rc = ensure_lds(osot_qp_sens_big_kernel, sensbig::lds_bytes(sensbig::kMaxVars, sensbig::kMaxRows));
+            if (rc != OSOT_OK) return rc;
+            if (device >= 0 && device < 64) raised |= 1ull << device;
+        }
+    }
+    SensBigArgs S;
+    S.s.b = *b;
+    sens_options(opt, &S.s.active_tol, &S.s.dual_tol, &S.s.rank_tol);
+    S.work = static_cast<double*>(workspace);
+    const int slots = sensbig::slots(b->n, b->nc);
+    const unsigned grid = (unsigned)(b->B < slots ? b->B : slots);
+    hipLaunchKernelGGL(osot_qp_sens_big_kernel, dim3(grid), dim3(sensbig::kThreads), lds, (hipStream_t)hip_stream, S);
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

@@ -6,7 +6,8 @@ results come back as tensors on the same device and stream -- no host copies, no
 
     qp_solve(H, g, A, lA, uA, l, u, ...)   B generic QPs in BackEnd convention through either back-end
     qp_multipliers(..., x)                 their multipliers and active sets (QPOasesBackEnd::getDualSolution / getActiveBounds)
-    qp_layer(H, g, A, lA, uA, l, u)        the active-set solve as a differentiable layer (n <= 64)
+    qp_layer(H, g, A, lA, uA, l, u)        the active-set solve as a differentiable layer (n <= 64; up to 128 with
+                                           workspace = qp_sens_workspace(B, n, nc), as qp_multipliers)
     ihqp_layer(stack, b, w, lo, up, ...)   the cascade of a BatchedStack as a differentiable layer over its assembled inputs (n <= 64)
     iHQP / nHQP                            the cascade front-ends on a BatchedStack, `solve()` returning dq as a tensor;
                                            iHQP.getObjective(i) / getDualSolution(i) / getActiveSet(i) / getSensitivityFlag(i) / getLevelQP(i) after a solve
@@ -146,11 +147,42 @@ def _sens_options(options):
     return C.byref(o)
 
 
-def qp_multipliers(H, g, A, lA, uA, l, u, x, status=None, eps_regularisation=2e2, options=None):
+def qp_sens_workspace(B, n, nc, device=None):
+    """the workspace qp_multipliers(..., workspace=) and qp_layer(..., workspace=) need for B QPs of n variables and nc rows
+    (osot_qp_sens_workspace_bytes): a uint8 tensor on the GPU, empty for n <= 64.  It is sized by the workgroups in flight, not by
+    B, and serves one call at a time."""
+    nbytes = C.c_size_t(0)
+    abi.check(abi.lib().osot_qp_sens_workspace_bytes(int(B), int(n), int(nc), C.byref(nbytes)), "osot_qp_sens_workspace_bytes")
+    if device is None:
+        device = torch.cuda.current_device()
+    dev = torch.device("cuda", device) if isinstance(device, int) else device
+    return torch.empty((nbytes.value,), dtype=torch.uint8, device=dev)
+
+
+def _sens_call(b, options, workspace, dev):
+    """osot_qp_sensitivity_batch, or with a workspace osot_qp_sensitivity_batch_ws, on the current stream of dev"""
+    stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    with torch.cuda.device(dev):
+        if workspace is None:
+            try:
+                abi.check(abi.lib().osot_qp_sensitivity_batch(C.byref(b), options, stream), "osot_qp_sensitivity_batch")
+            except RuntimeError as e:
+                if 64 < b.n <= 128:
+                    raise RuntimeError(f"{e}; with workspace=qp_sens_workspace(B, n, nc) the call takes up to 128 variables") from None
+                raise
+            return
+        if not isinstance(workspace, torch.Tensor) or workspace.device != dev or workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+            raise TypeError(f"workspace must be a contiguous uint8 tensor on {dev} (qp_sens_workspace(B, n, nc) makes it)")
+        abi.check(abi.lib().osot_qp_sensitivity_batch_ws(C.byref(b), options, _ptr(workspace), workspace.numel(), stream),
+                  "osot_qp_sensitivity_batch_ws")
+
+
+def qp_multipliers(H, g, A, lA, uA, l, u, x, status=None, eps_regularisation=2e2, options=None, workspace=None):
     """The multipliers and the active set of B QPs at their solutions x [B][n] (qp_solve's, or anybody's): what QPOasesBackEnd keeps as
     getDualSolution (nV + nC entries, the bounds first; QPOasesBackEnd.cpp:153-158) and getActiveBounds / getActiveConstraints.
     status [B] int32 (qp_solve's) or None = all solved.  options: dict with active_tol, dual_tol, rank_tol (0 or absent = 1e-8, 1e-9,
-    1e-11).  n <= 64; 65 .. 128 variables are not built (RuntimeError).
+    1e-11).  n <= 64; with workspace = qp_sens_workspace(B, n, nc) n goes up to 128 (without it 65 .. 128 variables are refused:
+    RuntimeError).
     Returns (y [B][n + nc] float64 in qpOASES' convention: H~ x + g = y_b + A' y_c, y > 0 on a lower side, y < 0 on an upper side;
     active [B][n + nc] int32: 0, -1 lower, +1 upper, 2 equality; flag [B] int32 OSOT_SENS_*: 0 unique, 1 degenerate (a valid one-sided
     answer), 2 skipped (not solved, x not finite or H + eps I not positive definite: zeros)), stream-ordered on the current stream."""
@@ -160,21 +192,19 @@ def qp_multipliers(H, g, A, lA, uA, l, u, x, status=None, eps_regularisation=2e2
     active = torch.empty((B, n + nc), dtype=torch.int32, device=dev)
     flag = torch.empty((B,), dtype=torch.int32, device=dev)
     b.y, b.active, b.flag = _ptr(y), _ptr(active), _ptr(flag)
-    with torch.cuda.device(dev):
-        abi.check(abi.lib().osot_qp_sensitivity_batch(C.byref(b), _sens_options(options), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)),
-                  "osot_qp_sensitivity_batch")
+    _sens_call(b, _sens_options(options), workspace, dev)
     return y, active, flag
 
 
 class _QpLayer(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, H, g, A, lA, uA, l, u, eps_regularisation, max_iter, hot, last):
+    def forward(ctx, H, g, A, lA, uA, l, u, eps_regularisation, max_iter, hot, last, workspace):
         x, status, iters = qp_solve(H, g, A, lA, uA, l, u, eps_regularisation=eps_regularisation, max_iter=max_iter, hot=hot)
         last.status, last.iterations = status, iters
         last.flag = torch.full((H.shape[0],), -1, dtype=torch.int32, device=H.device)      # filled by the backward pass
         ctx.save_for_backward(*[t for t in (H, g, A, lA, uA, l, u, x, status) if t is not None])
         ctx.present = [t is not None for t in (H, g, A, lA, uA, l, u)]
-        ctx.eps, ctx.last = eps_regularisation, last
+        ctx.eps, ctx.last, ctx.workspace = eps_regularisation, last, workspace
         return x
 
     @staticmethod
@@ -193,10 +223,8 @@ class _QpLayer(torch.autograd.Function):
                 setattr(b, name, _ptr(out))
             grads.append(out)
         ctx.last.bound = [name for name, o in zip(("H", "g", "A", "lA", "uA", "l", "u"), grads) if o is not None]
-        with torch.cuda.device(H.device):
-            abi.check(abi.lib().osot_qp_sensitivity_batch(C.byref(b), None, C.c_void_p(torch.cuda.current_stream(H.device).cuda_stream)),
-                      "osot_qp_sensitivity_batch")
-        return (*grads, None, None, None, None)
+        _sens_call(b, None, ctx.workspace, H.device)
+        return (*grads, None, None, None, None, None)
 
 
 class _QpLayerLast:
@@ -206,20 +234,22 @@ class _QpLayerLast:
     bound = ()
 
 
-def qp_layer(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=2e2, max_iter=0, hot=None):
+def qp_layer(H, g, A=None, lA=None, uA=None, l=None, u=None, eps_regularisation=2e2, max_iter=0, hot=None, workspace=None):
     """qp_solve through the active-set back-end as a differentiable layer: x [B][n] carries autograd's graph to H, g, A, lA, uA, l, u
     (those that require a gradient).  The backward pass is one launch of osot_qp_sensitivity_batch: the active set at x, its
     multipliers and one more solve of the same KKT system with the upstream gradient on the right-hand side; grad_H is symmetric
     (the derivative with respect to a symmetric H), an equality's gradient goes to its lower bound.  An instance that was not solved
     (status != 0) or that the backward pass skipped contributes a zero gradient; at a degenerate solution (flag 1) the gradient is a
     valid one-sided one.  `qp_layer.last` holds status, iterations and flag of the most recent call.
-    n <= 64 (ValueError above; the solve alone goes to 128 through qp_solve).  The OSQP-convention back-end is not offered as a layer:
-    its solutions stop at 1e-5, too far from a vertex to read the active set from."""
-    if H.dim() == 3 and H.shape[1] > 64:
-        raise ValueError("qp_layer: more than 64 variables (the backward pass is built for n <= 64; qp_solve alone takes up to 128)")
+    n <= 64 without a workspace (ValueError above; the solve alone goes to 128 through qp_solve); with workspace =
+    qp_sens_workspace(B, n, nc), which the backward pass hands to osot_qp_sensitivity_batch_ws, n goes up to 128.  The
+    OSQP-convention back-end is not offered as a layer: its solutions stop at 1e-5, too far from a vertex to read the active set from."""
+    if H.dim() == 3 and H.shape[1] > 64 and workspace is None:
+        raise ValueError("qp_layer: more than 64 variables (without a workspace the backward pass is built for n <= 64; pass "
+                         "workspace=qp_sens_workspace(B, n, nc) for up to 128; qp_solve alone takes up to 128)")
     last = _QpLayerLast()
     qp_layer.last = last
-    return _QpLayer.apply(H, g, A, lA, uA, l, u, eps_regularisation, max_iter, hot, last)
+    return _QpLayer.apply(H, g, A, lA, uA, l, u, eps_regularisation, max_iter, hot, last, workspace)
 
 
 qp_layer.last = _QpLayerLast()
