@@ -1371,8 +1371,11 @@ int osot_qp_sensitivity_batch_ws(const osot_qp_sens_batch* b, const osot_qp_sens
 /* ---- the QP of every level of the batched iHQP cascade, its multipliers, active set and objective (opensot_amd/csrc/osot_ihqp_sens.h)
  * What iHQP exposes besides solve(): getBackEnd(i) (the level's H, g, A, lA, uA, l, u, iHQP.cpp:381-389, BackEnd.h), on the default
  * back-end the dual solution and the working set of that level (QPOasesBackEnd.h:163-172), and getObjective(i).  For handles of
- * osot_solver_create (the wavefront route, n <= 64); a handle of osot_solver_create_wide is refused with OSOT_ERR_UNSUPPORTED before
- * any device is touched.
+ * osot_solver_create (the wavefront route, n <= 64: one wavefront per instance) and for handles of osot_solver_create_wide whose
+ * plan has 65 .. 128 variables (one 256-thread workgroup per instance, opensot_amd/csrc/osot_ihqp_sens_wide.h, and
+ * osot_qp_sensitivity_batch_ws's kernel for the multipliers): the same contract, the same results to the tolerances of the tests.
+ * A handle of osot_solver_create_wide whose plan has n <= 64 is refused with OSOT_ERR_UNSUPPORTED before any device is touched:
+ * such a plan belongs on osot_solver_create.
  *
  * THE LEVEL QP, for the inputs of an osot_qp_batch and the x_levels its solve left behind:
  *   H [B][n][n] ........ A_k' W_k A_k, full and symmetric to the bit, WITHOUT eps_abs: the stored rows (w[k] on the diagonal, or the
@@ -1391,7 +1394,8 @@ int osot_qp_sensitivity_batch_ws(const osot_qp_sens_batch* b, const osot_qp_sens
 typedef struct osot_level_qp { double *H, *g, *A, *lA, *uA, *l, *u; } osot_level_qp;   /* device pointers, all required */
 /* rows of the QP of `level` (host only).  OSOT_ERR_INVALID: a null argument, level outside 0 .. n_levels-1. */
 int osot_ihqp_level_rows(osot_solver* s, int level, int* rows);
-/* One launch, stream-ordered, no allocation, capturable.  batch: as for osot_ihqp_solve, with x_levels (its level_active and the
+/* One launch, stream-ordered, no allocation, capturable (a wide handle: after one eager call on the device -- the kernel's LDS,
+ * 8 (64 (n | 1) + n) bytes, is 67 072 at n = 128, and the first call raises the limit, a host-side setting).  batch: as for osot_ihqp_solve, with x_levels (its level_active and the
  * handle's osot_solver_set_task_active flags are the ones of the solve).  OSOT_ERR_INVALID: a null argument or member of out, level
  * out of range, B outside 0 .. max_batch, what osot_ihqp_solve refuses of a batch, x_levels NULL for level > 0. */
 int osot_ihqp_level_qp(osot_solver* s, const osot_qp_batch* batch, int level, const osot_level_qp* out, void* hip_stream);
@@ -1403,14 +1407,16 @@ int osot_ihqp_level_qp(osot_solver* s, const osot_qp_batch* batch, int level, co
  *   y[k] .......... [B][n + rows_k] qpOASES' sign, the n bounds first (rows_k: osot_ihqp_level_rows); active[k] likewise; flag[k] [B].
  *                   One pointer per level, each may be NULL.
  *   objective ..... [B][n_levels] or NULL: 1/2 x_k'(H_k + eps_abs I) x_k + g_k' x_k, qpOASES' getObjVal() of the level
- *   workspace ..... device memory of the caller, at least osot_ihqp_sens_workspace_bytes, 8-byte aligned
+ *   workspace ..... device memory of the caller, at least osot_ihqp_sens_workspace_bytes, 8-byte aligned (a wide handle: 16-byte)
  * An instance whose status is not OSOT_STATUS_SOLVED is OSOT_SENS_SKIPPED at every level (zeros); so is every instance at a level
  * that level_active switches off.  Nothing non-finite is written.
  * Stream-ordered, no allocation, no synchronisation, capturable (33 .. 64 variables: after one eager call on the device, see
- * osot_qp_sensitivity_batch).  Refused before any device is touched (osot_last_error() says why): a wide handle
- * (OSOT_ERR_UNSUPPORTED); with OSOT_ERR_INVALID a null argument, B outside 0 .. max_batch, what osot_ihqp_solve refuses of qp,
- * x_levels or status NULL, workspace NULL or smaller than needed, a bad tolerance, an output that overlaps an input, the workspace
- * or another output (the workspace by its byte range; the others by their first address).  "Nothing non-finite is written" holds
+ * osot_qp_sensitivity_batch; a wide handle: always after one eager call, which raises the LDS limits of the level kernel and of
+ * osot_qp_sensitivity_batch_ws's kernel).  Refused before any device is touched (osot_last_error() says why): a wide handle whose
+ * plan has n <= 64 (OSOT_ERR_UNSUPPORTED); with OSOT_ERR_INVALID a null argument, B outside 0 .. max_batch, what osot_ihqp_solve
+ * refuses of qp, x_levels or status NULL, workspace NULL, misaligned or smaller than needed, a bad tolerance, an input inside the
+ * workspace, an output that overlaps an input, the workspace or another output (the workspace by its byte range; the others by
+ * their first address).  "Nothing non-finite is written" holds
  * for the outputs: the workspace of an instance that was not solved holds whatever x_levels held.
  *
  * BACKWARD (grad_dq given): the gradients of a loss with respect to the assembled inputs of the cascade, given grad_dq = d loss / d dq.
@@ -1443,7 +1449,11 @@ typedef struct osot_ihqp_sens_batch {
 } osot_ihqp_sens_batch;
 /* bytes of workspace for B instances (host only), rows = the last level's.  Forward: 8 (B (n n + rows n + 2 rows + 4 n) + (B + 1) / 2):
  * one level QP, x of the level and a flag per instance.  want_backward adds 8 B (3 n + 2 rows + L n) (dx, the QP's bound gradients,
- * gx of every level), want_grad_A (grad_A[k] or grad_C will be asked for) 8 B rows n more (the QP's grad_A). */
+ * gx of every level), want_grad_A (grad_A[k] or grad_C will be asked for) 8 B rows n more (the QP's grad_A).
+ * A wide handle (65 .. 128 variables): that sum rounded up to 16 bytes, plus osot_qp_sens_workspace_bytes(B, n, rows) -- min(B, slots)
+ * slices of 8 n (2n + 2) bytes for the multiplier kernel, slots = 256 (160 KiB / its LDS at (n, rows), at most 4); every level is
+ * launched with that many workgroups (the last level has the most rows, so the fewest fit).  OSOT_ERR_UNSUPPORTED: a wide handle
+ * whose plan has n <= 64. */
 int osot_ihqp_sens_workspace_bytes(osot_solver* s, int B, int want_backward, int want_grad_A, unsigned long long* bytes);
 int osot_ihqp_sensitivity(osot_solver* s, const osot_ihqp_sens_batch* b, const osot_qp_sens_options* opt, void* hip_stream);
 

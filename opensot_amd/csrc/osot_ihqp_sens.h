@@ -10,7 +10,9 @@
 //                                   that is switched off, the zeros of a SKIPPED instance)
 //   osot_ihqp_pullback_kernel ..... one wavefront per instance: the backward pass's link between the levels (below)
 // The multipliers, and each level's KKT solve of the backward pass, are osot_qp_sens_kernel (osot_qp_sens.h), unchanged, on the
-// materialised QP.
+// materialised QP.  A handle of osot_solver_create_wide whose plan has 65 .. 128 variables passes the same checks and the same
+// schedule (ihqp_sens_levels) with the workgroup kernels of osot_ihqp_sens_wide.h and osot_qp_sens_big_kernel; its workspace is
+// ihqp_wide_workspace_bytes.  A wide handle whose plan has n <= 64 stays refused: such a plan belongs on osot_solver_create.
 //
 // THE ROUTE of the level kernel.  Rows are staged through LDS coalesced (lane = column) in tiles of kLevelTile rows (odd row
 // stride: a lane-per-row walk at one column has no bank conflict).  H: lane = column j keeps column j of H in registers, entry
@@ -24,6 +26,7 @@
 #include <osot_mi355x.h>
 #include "osot_plan_shape.h"
 #include "osot_qp_sens.h"
+#include "osot_qp_sens_big.h"   // sensbig::workspace_bytes, slots: the wide route's share of the workspace
 
 namespace osot {
 
@@ -94,6 +97,22 @@ inline IhqpSensWorkspace ihqp_sens_workspace(const LevelPlan& P, long long B, bo
     return W;
 }
 
+// The workspace of osot_ihqp_sensitivity on a wide handle, in bytes: the arrays of ihqp_sens_workspace (the level QP, x, the flags,
+// with grad_dq the level's gradients), rounded up to 16 bytes, then the Y slices of osot_qp_sens_big_kernel,
+// sensbig::workspace_bytes(B, n, rows of the last level) -- min(B, slots(n, rows_last)) slices of n (2n + 2) doubles.  The last level
+// has the most rows, hence the largest LDS block and the fewest slots: every level is launched with that many workgroups.
+inline unsigned long long ihqp_wide_front_bytes(const LevelPlan& P, long long B, bool back, bool grad_A) {
+    return (((unsigned long long)ihqp_sens_workspace(P, B, back, grad_A).total * sizeof(double)) + 15ull) & ~15ull;
+}
+inline unsigned long long ihqp_wide_workspace_bytes(const LevelPlan& P, long long B, bool back, bool grad_A) {
+    return ihqp_wide_front_bytes(P, B, back, grad_A) + (unsigned long long)sensbig::workspace_bytes((int)B, P.n, level_qp_rows(P, P.L - 1));
+}
+// workgroups of every osot_qp_sens_big_kernel launch of a call
+inline int ihqp_wide_sens_grid(const LevelPlan& P, int B) {
+    const int s = sensbig::slots(P.n, level_qp_rows(P, P.L - 1));
+    return B < s ? B : s;
+}
+
 // the gradient outputs of a call (osot_ihqp_sens_batch's)
 struct IhqpGrads { double *b[OSOT_KMAX_LEVELS], *w[OSOT_KMAX_LEVELS], *c[OSOT_KMAX_LEVELS], *A[OSOT_KMAX_LEVELS], *C, *lo, *up, *l, *u; };
 struct PullbackArgs {
@@ -123,7 +142,7 @@ inline bool ihqp_wants_grad_A(const osot_ihqp_sens_batch& b, int L) {
 // task_active: the handle's Task::setActive flags (null: all active), as make_plan_shape takes them
 inline int level_qp_check(const osot_plan_desc& plan, int wide, int max_batch, const unsigned char* task_active, const osot_qp_batch* b, int level,
                           const osot_level_qp* out, LevelQpArgs& Q, const char** why) {
-    if (wide) { *why = "the level QPs are built for handles of osot_solver_create (one wavefront per instance, n <= 64), not for the wide route"; return OSOT_ERR_UNSUPPORTED; }
+    if (wide && plan.n <= OSOT_MAX_VARS) { *why = "the level QPs are built for handles of osot_solver_create (one wavefront per instance, n <= 64), not for the wide route"; return OSOT_ERR_UNSUPPORTED; }
     if (!b || !out) { *why = "null argument"; return OSOT_ERR_INVALID; }
     if (level < 0 || level >= plan.n_levels) { *why = "level out of range"; return OSOT_ERR_INVALID; }
     if (b->B < 0 || b->B > max_batch) { *why = "batch size exceeds max_batch"; return OSOT_ERR_INVALID; }
@@ -142,7 +161,7 @@ inline int level_qp_check(const osot_plan_desc& plan, int wide, int max_batch, c
 // the checks of osot_ihqp_sensitivity; Q receives the plan shape's batch pointers
 inline int ihqp_sens_check(const osot_plan_desc& plan, int wide, int max_batch, const unsigned char* task_active, const osot_ihqp_sens_batch* b,
                            const osot_qp_sens_options* o, LevelQpArgs& Q, const char** why) {
-    if (wide) { *why = "per-level multipliers are built for handles of osot_solver_create (one wavefront per instance, n <= 64), not for the wide route"; return OSOT_ERR_UNSUPPORTED; }
+    if (wide && plan.n <= OSOT_MAX_VARS) { *why = "per-level multipliers are built for handles of osot_solver_create (one wavefront per instance, n <= 64), not for the wide route"; return OSOT_ERR_UNSUPPORTED; }
     if (!b) { *why = "null argument"; return OSOT_ERR_INVALID; }
     if (b->qp.B < 0 || b->qp.B > max_batch) { *why = "batch size exceeds max_batch"; return OSOT_ERR_INVALID; }
     if (o) {
@@ -174,9 +193,11 @@ inline int ihqp_sens_check(const osot_plan_desc& plan, int wide, int max_batch, 
     if (rc != OSOT_OK) return rc;
     if (!q.x_levels || !q.status) { *why = "x_levels / status of the solve is null"; return OSOT_ERR_INVALID; }
     if (!b->workspace) { *why = "workspace is null"; return OSOT_ERR_INVALID; }
-    const unsigned long long need = (unsigned long long)ihqp_sens_workspace(Q.P, q.B, b->grad_dq != nullptr, ihqp_wants_grad_A(*b, L)).total * sizeof(double);
+    const unsigned long long need = wide ? ihqp_wide_workspace_bytes(Q.P, q.B, b->grad_dq != nullptr, ihqp_wants_grad_A(*b, L))
+                                         : (unsigned long long)ihqp_sens_workspace(Q.P, q.B, b->grad_dq != nullptr, ihqp_wants_grad_A(*b, L)).total * sizeof(double);
     if (b->workspace_bytes < need) { *why = "workspace is smaller than osot_ihqp_sens_workspace_bytes"; return OSOT_ERR_INVALID; }
-    if (reinterpret_cast<unsigned long long>(b->workspace) % sizeof(double)) { *why = "workspace is not 8-byte aligned"; return OSOT_ERR_INVALID; }
+    if (!wide && reinterpret_cast<unsigned long long>(b->workspace) % sizeof(double)) { *why = "workspace is not 8-byte aligned"; return OSOT_ERR_INVALID; }
+    if (wide && reinterpret_cast<unsigned long long>(b->workspace) % 16) { *why = "workspace is not 16-byte aligned"; return OSOT_ERR_INVALID; }
     const void* in[16 + 6 * OSOT_MAX_LEVELS] = {q.C, q.lo, q.up, q.l, q.u, q.dq, q.x_levels, q.status, q.iterations, q.b_reg, q.accepted_slack, q.A_reg, b->grad_dq};
     int ni = 13;
     for (int k = 0; k < L; ++k) { in[ni++] = q.A[k]; in[ni++] = q.b[k]; in[ni++] = q.w[k]; in[ni++] = q.c[k]; in[ni++] = q.WA[k]; in[ni++] = q.Wb[k]; }

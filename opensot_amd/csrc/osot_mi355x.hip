@@ -28,6 +28,7 @@
 #include "osot_qp_sens.h"
 #include "osot_qp_sens_big.h"
 #include "osot_ihqp_sens.h"
+#include "osot_ihqp_sens_wide.h"
 #include "osot_nhqp_host.h"
 #include "osot_admm.h"
 #include "osot_qp_big.h"
@@ -1661,13 +1662,10 @@ int osot_qp_sens_workspace_bytes(int B, int n, int nc, size_t* bytes) {
     *bytes = sensbig::workspace_bytes(B, n, nc);
     return OSOT_OK;
 }
-int osot_qp_sensitivity_batch_ws(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* workspace, size_t workspace_bytes,
-                                 void* hip_stream) {
-    const char* why = "";
-    int rc = sens_ws_check(b, opt, workspace, workspace_bytes, &why);
-    if (rc != OSOT_OK) return fail(rc, std::string("osot_qp_sensitivity_batch_ws: ") + why);
-    if (b->B == 0) return OSOT_OK;
-    if (b->n <= OSOT_MAX_VARS) return sens_launch(b, opt, hip_stream);
+// the launch of osot_qp_sens_big_kernel on a checked batch of 65 .. 128 variables: `grid` workgroups (at most slots(n, nc)) walk the
+// batch, each on its own slice of `workspace` (osot_ihqp_sensitivity on a wide handle launches it once per level)
+static int sens_big_launch(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* workspace, unsigned grid, void* hip_stream) {
+    int rc = OSOT_OK;
     // 41.3 KiB of LDS at (65, 40) lets three workgroups share a CU, 145.1 KiB at (128, 24) one (derived: sensbig::lds_bytes).  The limit is
     // raised to the largest there is, ONCE per device: later launches, captured ones included, only launch
     const size_t lds = sensbig::lds_bytes(b->n, b->nc);
@@ -1685,11 +1683,19 @@ int osot_qp_sensitivity_batch_ws(const osot_qp_sens_batch* b, const osot_qp_sens
     S.s.b = *b;
     sens_options(opt, &S.s.active_tol, &S.s.dual_tol, &S.s.rank_tol);
     S.work = static_cast<double*>(workspace);
-    const int slots = sensbig::slots(b->n, b->nc);
-    const unsigned grid = (unsigned)(b->B < slots ? b->B : slots);
     hipLaunchKernelGGL(osot_qp_sens_big_kernel, dim3(grid), dim3(sensbig::kThreads), lds, (hipStream_t)hip_stream, S);
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
+}
+int osot_qp_sensitivity_batch_ws(const osot_qp_sens_batch* b, const osot_qp_sens_options* opt, void* workspace, size_t workspace_bytes,
+                                 void* hip_stream) {
+    const char* why = "";
+    const int rc = sens_ws_check(b, opt, workspace, workspace_bytes, &why);
+    if (rc != OSOT_OK) return fail(rc, std::string("osot_qp_sensitivity_batch_ws: ") + why);
+    if (b->B == 0) return OSOT_OK;
+    if (b->n <= OSOT_MAX_VARS) return sens_launch(b, opt, hip_stream);
+    const int slots = sensbig::slots(b->n, b->nc);
+    return sens_big_launch(b, opt, workspace, (unsigned)(b->B < slots ? b->B : slots), hip_stream);
 }
 
 // ---- the level QPs of the cascade, their multipliers, active sets and objectives (osot_ihqp_sens.h) -------------------------------
@@ -1699,6 +1705,25 @@ int osot_ihqp_level_rows(osot_solver* s, int level, int* rows) {
     LevelPlan P;
     make_plan_shape(s->plan, nullptr, nullptr, P);
     *rows = level_qp_rows(P, level);
+    return OSOT_OK;
+}
+
+// the wide route (65 .. 128 variables, osot_ihqp_sens_wide.h): one 256-thread workgroup per instance.  The level kernel's LDS is
+// 67 072 bytes at n = 128, above the default limit: it is raised to that, ONCE per device, on the first call -- one eager call must
+// come before a capture (osot_qp_sens_big_kernel's limit is raised the same way by sens_big_launch)
+static int level_qp_wide_launch(const LevelQpArgs& Q, hipStream_t st) {
+    const size_t lds = (size_t)ihqpwide::level_lds_bytes(Q.P.n);
+    if (lds > 64 * 1024) {
+        static unsigned long long raised = 0ull;     // bit d: done on device d (benign if two threads both do it)
+        int device = 0;
+        HIP_TRY(hipGetDevice(&device));
+        if (device < 0 || device >= 64 || !((raised >> device) & 1ull)) {
+            const int rc = ensure_lds(osot_ihqp_level_qp_wide_kernel, (size_t)ihqpwide::level_lds_bytes(ihqpwide::kMaxVars));
+            if (rc != OSOT_OK) return rc;
+            if (device >= 0 && device < 64) raised |= 1ull << device;
+        }
+    }
+    hipLaunchKernelGGL(osot_ihqp_level_qp_wide_kernel, dim3((unsigned)Q.D.B), dim3(ihqpwide::kThreads), lds, st, Q);
     return OSOT_OK;
 }
 
@@ -1717,18 +1742,24 @@ int osot_ihqp_level_qp(osot_solver* s, const osot_qp_batch* b, int level, const 
     if (b->B == 0) return OSOT_OK;
     DeviceGuard guard(s->device);
     if (!guard.ok) return fail(OSOT_ERR_HIP, "hipSetDevice failed");
-    level_qp_launch(Q, (hipStream_t)hip_stream);
+    if (s->wide) {
+        const int r = level_qp_wide_launch(Q, (hipStream_t)hip_stream);
+        if (r != OSOT_OK) return r;
+    } else {
+        level_qp_launch(Q, (hipStream_t)hip_stream);
+    }
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }
 
 int osot_ihqp_sens_workspace_bytes(osot_solver* s, int B, int want_backward, int want_grad_A, unsigned long long* bytes) {
     if (!s || !bytes) return fail(OSOT_ERR_INVALID, "osot_ihqp_sens_workspace_bytes: null argument");
-    if (s->wide) return fail(OSOT_ERR_UNSUPPORTED, "osot_ihqp_sens_workspace_bytes: per-level multipliers are built for handles of osot_solver_create, not for the wide route");
+    if (s->wide && s->plan.n <= OSOT_MAX_VARS) return fail(OSOT_ERR_UNSUPPORTED, "osot_ihqp_sens_workspace_bytes: per-level multipliers are built for handles of osot_solver_create, not for the wide route");
     if (B < 0 || B > s->max_batch) return fail(OSOT_ERR_INVALID, "osot_ihqp_sens_workspace_bytes: batch size exceeds max_batch");
     LevelPlan P;
     make_plan_shape(s->plan, nullptr, nullptr, P);
-    *bytes = (unsigned long long)ihqp_sens_workspace(P, B, want_backward != 0, want_grad_A != 0).total * sizeof(double);
+    *bytes = s->wide ? ihqp_wide_workspace_bytes(P, B, want_backward != 0, want_grad_A != 0)
+                     : (unsigned long long)ihqp_sens_workspace(P, B, want_backward != 0, want_grad_A != 0).total * sizeof(double);
     return OSOT_OK;
 }
 
@@ -1750,7 +1781,21 @@ int osot_ihqp_sensitivity(osot_solver* s, const osot_ihqp_sens_batch* b, const o
         void zero(void* p, size_t bytes) { if (bytes) (void)hipMemsetAsync(p, 0, bytes, st); }
         void copy(void* dst, const void* src, size_t bytes) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st); }
     } go{(hipStream_t)hip_stream, opt};
-    if (const int r = ihqp_sens_levels(Q, b, go)) return r;
+    if (s->wide) {
+        // the same schedule with the workgroup kernels; the Y slices of osot_qp_sens_big_kernel follow the schedule's arrays
+        struct {
+            hipStream_t st; const osot_qp_sens_options* opt; void* slices; unsigned grid; int rc;
+            void level_qp(const LevelQpArgs& q) { const int r = level_qp_wide_launch(q, st); if (rc == OSOT_OK) rc = r; }
+            int sens(const osot_qp_sens_batch& S) { return rc != OSOT_OK ? rc : sens_big_launch(&S, opt, slices, grid, st); }
+            void objective(const ObjectiveArgs& O) { hipLaunchKernelGGL(osot_ihqp_objective_wide_kernel, dim3((unsigned)O.B), dim3(ihqpwide::kThreads), (size_t)ihqpwide::objective_lds_bytes(O.n), st, O); }
+            void pullback(const PullbackArgs& R) { hipLaunchKernelGGL(osot_ihqp_pullback_wide_kernel, dim3((unsigned)R.D.B), dim3(ihqpwide::kThreads), (size_t)ihqpwide::pullback_lds_bytes(R.P.n), st, R); }
+            void zero(void* p, size_t bytes) { if (bytes) (void)hipMemsetAsync(p, 0, bytes, st); }
+            void copy(void* dst, const void* src, size_t bytes) { (void)hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st); }
+        } wgo{(hipStream_t)hip_stream, opt,
+              static_cast<char*>(b->workspace) + ihqp_wide_front_bytes(Q.P, b->qp.B, b->grad_dq != nullptr, ihqp_wants_grad_A(*b, Q.P.L)),
+              (unsigned)ihqp_wide_sens_grid(Q.P, b->qp.B), OSOT_OK};
+        if (const int r = ihqp_sens_levels(Q, b, wgo)) return r;
+    } else if (const int r = ihqp_sens_levels(Q, b, go)) return r;
     HIP_TRY(hipGetLastError());
     return OSOT_OK;
 }

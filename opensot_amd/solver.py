@@ -284,7 +284,9 @@ class BatchedStack:
     def level_qp(self, k, B):
         """the QP that the cascade solved at level k for the B instances of the last solve() (iHQP::getBackEnd(k): H, g, A, lA, uA, l,
         u of BackEnd.h), built on the device from the stack's buffers and x_levels: dict of tensors H [B][n][n] (without eps), g [B][n],
-        A [B][rows][n], lA, uA [B][rows], l, u [B][n]; stream-ordered.  The wavefront route only."""
+        A [B][rows][n], lA, uA [B][rows], l, u [B][n]; stream-ordered.  Both routes: the wavefront kernels up to 64 variables, the
+        workgroup kernels on a wide stack of 65 .. 128 (a wide stack with n <= 64 is refused: such a plan belongs on the wavefront
+        route).  On a wide stack one eager call must come before a graph capture (the first call raises a kernel's LDS limit)."""
         n, rows = self.plan.n, self.level_rows(k)
         f64 = dict(dtype=torch.float64, device=self.device)
         out = dict(H=torch.empty((B, n, n), **f64), g=torch.empty((B, n), **f64), A=torch.empty((B, rows, n), **f64),
@@ -301,14 +303,15 @@ class BatchedStack:
         return out
 
     def sens_workspace(self, B, backward=False, grad_A=False):
-        """the workspace of multipliers() / backward() for B instances (float64, osot_ihqp_sens_workspace_bytes); kept and reused while
-        it is large enough"""
+        """the workspace of multipliers() / backward() for B instances (float64, osot_ihqp_sens_workspace_bytes; 16-byte aligned, which
+        the wide route asks for); kept and reused while it is large enough"""
         v = C.c_ulonglong(0)
         abi.check(self._lib.osot_ihqp_sens_workspace_bytes(self._h, int(B), int(bool(backward)), int(bool(grad_A)), C.byref(v)),
                   "osot_ihqp_sens_workspace_bytes")
         ws = getattr(self, "_sens_ws", None)
         if ws is None or ws.numel() * 8 < v.value:
-            ws = self._sens_ws = torch.empty((max(1, v.value // 8),), dtype=torch.float64, device=self.device)
+            raw = torch.empty((max(1, v.value // 8) + 1,), dtype=torch.float64, device=self.device)
+            ws = self._sens_ws = raw[(raw.data_ptr() % 16) // 8:][:max(1, v.value // 8)]
         return ws, v.value
 
     def multipliers(self, B, options=None, out=None):
@@ -316,8 +319,8 @@ class BatchedStack:
         default back-end getDualSolution, getActiveBounds / getActiveConstraints, getObjVal).  Returns dict(y, active, flag: lists
         with one tensor per level, y[k] [B][n + level_rows(k)] in qpOASES' sign with the bounds first, active[k] likewise (0, -1
         lower, +1 upper, 2 equality), flag[k] [B] OSOT_SENS_*; objective [B][L]).  out: such a dict to write into (a captured graph
-        replays into the same tensors); options: dict with active_tol, dual_tol, rank_tol.  Stream-ordered; the wavefront route only;
-        needs want_levels."""
+        replays into the same tensors); options: dict with active_tol, dual_tol, rank_tol.  Stream-ordered; both routes, as
+        level_qp(); needs want_levels."""
         n, L = self.plan.n, self.plan.L
         if out is None:
             f64 = dict(dtype=torch.float64, device=self.device)
@@ -346,7 +349,7 @@ class BatchedStack:
         Returns a dict shaped as the stack's own buffers: b, w, c (lists, one tensor per level: [B][m_k], [B][m_k], [B][n]), lo, up
         [B][nc], l, u [B][n] (None where the stack has no such buffer), with want_A also A (list, [B][ma_k][n] or None) and C
         [B][nc_stored][n]; and flag (list, [B] OSOT_SENS_* per level: 1 = a valid one-sided gradient, 2 = skipped, zero gradient).
-        Refused (RuntimeError with the reason): a wide stack, a plan with a dense-weight level or a regularisation task."""
+        Refused (RuntimeError with the reason): a wide stack with n <= 64, a plan with a dense-weight level or a regularisation task."""
         n, L = self.plan.n, self.plan.L
         if not (isinstance(grad_dq, torch.Tensor) and grad_dq.is_cuda and grad_dq.device == self.device and grad_dq.dtype == torch.float64
                 and grad_dq.is_contiguous() and tuple(grad_dq.shape) == (B, n)):

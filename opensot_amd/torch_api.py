@@ -285,16 +285,17 @@ class _IhqpLayerLast:
 
 
 def ihqp_layer(stack, b, w=None, lo=None, up=None, l=None, u=None, A=None, C=None):
-    """The cascade of a wavefront-route BatchedStack as a differentiable layer over its ASSEMBLED inputs: b, w, A are lists with one
+    """The cascade of a BatchedStack (the wavefront route, or the wide route with 65 .. 128 variables) as a differentiable layer over its ASSEMBLED inputs: b, w, A are lists with one
     tensor per level ([B][m_k], [B][m_k], [B][ma_k][n]; an entry, or the whole argument, may be None: the stack's buffer is used as it
     is), lo, up [B][nc], l, u [B][n], C [B][nc_stored][n].  The tensors are copied into the stack's buffers, the stack is solved, and dq
     [B][n] comes back carrying autograd's graph to those of them that require a gradient.  The backward pass is
     BatchedStack.backward on the stack's buffers and x_levels AS THEY ARE THEN: run it before the stack is solved again.  An instance
     that was not solved contributes a zero gradient; at a degenerate level the gradient is a valid one-sided one.  `ihqp_layer.last`
-    holds status and the levels' flags of the most recent call.  Raises before solving on a wide stack and on a plan with a
-    dense-weight level or a regularisation task (the backward pass is not built for them)."""
+    holds status and the levels' flags of the most recent call.  Raises before solving on a wide stack with n <= 64 (such a plan
+    belongs on the wavefront route) and on a plan with a dense-weight level or a regularisation task (the backward pass is not built
+    for them)."""
     plan = stack.plan
-    if stack.route != "wavefront":
+    if stack.route != "wavefront" and plan.n <= abi.MAX_VARS:
         raise ValueError("ihqp_layer: the backward pass is built for the wavefront route (n <= 64), not for a wide stack")
     if plan.regularisation is not None or any(plan.dense_level(k) for k in range(plan.L)):
         raise ValueError("ihqp_layer: the backward pass is not built for plans with a dense-weight level or a regularisation task")
