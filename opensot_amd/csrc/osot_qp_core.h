@@ -157,6 +157,40 @@ __device__ __forceinline__ void lean_row(const LeanRows& lr, int row, unsigned l
         if (in) { addr = stored ? a : safe; ucol = stored ? -1 : q - maj; }
     }
 }
+// The same for N rows of a LANE's own (0 <= row[i] < optoff[nlev]): ONE loop over the levels around the rows.  What a level contributes is
+// wave-uniform -- the address of its stored row q = row - optoff[j] is A_j + ((inst ma_j + q) 32) 8 = base_j + 256 row with base_j a
+// scalar, and its unit rows start at table row optoff[j] + ma_j -- so a row costs one compare and the selects of (base, first unit row)
+// per level BOUNDARY and one multiply-add at the end, instead of the whole address arithmetic per level.  Same addresses, same ucol.
+// PRECONDITION (what lean_row does not need): every row[i] IS a row of the table, i.e. optoff[nlev] > 0 and optoff = the prefix sums of
+// m -- a row at or beyond optoff[nlev] would come out as a row of the last level instead of (safe, -1).  The one caller passes
+// min(row, 0 if row >= n_eq) with 8 <= n_eq <= optoff[nlev] (gi_solve takes the elimination only from 8 equalities on).
+template <int N>
+__device__ __forceinline__ void lean_rows(const LeanRows& lr, const int (&row)[N], unsigned long long safe, unsigned long long (&addr)[N], int (&ucol)[N]) {
+    auto level_base = [&](int j) {
+        return reinterpret_cast<unsigned long long>(lr.A[j]) + (unsigned long long)(((lr.inst * lr.ma[j] - lr.optoff[j]) * 32) * 8);
+    };
+    const bool none = lr.nlev <= 0;
+    unsigned long long base[N];
+    int ufirst[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) { base[i] = level_base(0); ufirst[i] = lr.optoff[0] + lr.ma[0]; }
+    for (int j = 1; j < lr.nlev; ++j) {
+        const int o = lr.optoff[j], uj = o + lr.ma[j];
+        const unsigned long long bj = level_base(j);
+#pragma unroll
+        for (int i = 0; i < N; ++i) {
+            const bool at = row[i] >= o;
+            base[i] = at ? bj : base[i];
+            ufirst[i] = at ? uj : ufirst[i];
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        const bool unit = row[i] >= ufirst[i];
+        addr[i] = (unit || none) ? safe : base[i] + 256ull * (unsigned long long)row[i];
+        ucol[i] = (unit && !none) ? row[i] - ufirst[i] : -1;
+    }
+}
 __device__ __forceinline__ double lean_row_elem(const LeanRows& lr, int row, unsigned long long safe, int col) {   // (row is wave-uniform)
     unsigned long long addr; int ucol;
     lean_row(lr, row, safe, addr, ucol);
@@ -729,14 +763,22 @@ __device__ inline int nullspace_equalities32(const WaveCtx<32>& w, int n_eq, dou
         unsigned long long rp[8];   // the row's address (LEAN: safe_row for a unit row), or its table entry
         int uc[8];                  // LEAN: the unit row's column, -1 for a stored row
         double ld[16];
+        if constexpr (LEAN) {           // (the list is the table itself; n_eq = optoff[nlev] rows)
+            int rw[8];
 #pragma unroll
-        for (int I = 0; I < 2; ++I)
+            for (int I = 0; I < 2; ++I)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = 16 * I + tq + 4 * r;
-                if constexpr (LEAN) lean_row(lr, (row < n_eq) ? row : 0, w.safe_row, rp[4 * I + r], uc[4 * I + r]);   // (the list is the table itself)
-                else { rp[4 * I + r] = w.rptr[w.eqlist[(row < n_eq) ? row : 0]]; uc[4 * I + r] = 0; }
-            }
+                for (int r = 0; r < 4; ++r) { const int row = 16 * I + tq + 4 * r; rw[4 * I + r] = (row < n_eq) ? row : 0; }
+            lean_rows<8>(lr, rw, w.safe_row, rp, uc);
+        } else {
+#pragma unroll
+            for (int I = 0; I < 2; ++I)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = 16 * I + tq + 4 * r;
+                    rp[4 * I + r] = w.rptr[w.eqlist[(row < n_eq) ? row : 0]]; uc[4 * I + r] = 0;
+                }
+        }
         const int c0 = (LEAN || ta < n) ? ta : 0, c1 = (LEAN || 16 + ta < n) ? 16 + ta : 0;
 #pragma unroll
         for (int I = 0; I < 2; ++I)
